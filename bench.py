@@ -17,7 +17,11 @@ torchrun (WORLD_SIZE set: it must equal --gpus), or, when `--gpus N` is given
 without a torchrun environment, from N rank processes this script starts
 itself before anything here touches a GPU (launch_ranks).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does what that line's headline
+figure needs: set-up, warm-up, the timed steps.  With --full the counting pass
+(division paths, executed-work roofline), the time-to-first-witness search and
+the CPU baselines with their parity checks follow the timed steps, and the
+line carries their results too.
 """
 import argparse
 import json
@@ -52,6 +56,14 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch-log2", type=int, default=22, help="candidates per GPU per step = 2**k")
     ap.add_argument("--nodes", type=int, default=10000)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the counting pass "
+                         "(division paths, executed-work roofline), the time-to-first-witness search and the CPU "
+                         "baselines with their parity checks (each has its own --no-... switch); without it the "
+                         "run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float64): "
+                         "found.npy, the lowest satisfying index, and stats.npy, the launch's counters")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline sample budget")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ttfw", action="store_true", help="skip the time-to-first-witness search")
@@ -237,9 +249,12 @@ def main():
             found_any = found if found_any is None else min(found_any, found)
     barrier()
     elapsed = time.perf_counter() - t0
-    # the counting pass (untimed): the same K launches with the counters on
-    recount = found_any if args.no_recount else None
-    for k in (range(args.warmup, args.warmup + args.steps) if not args.no_recount else ()):
+    if args.dump_outputs and args.steps > 0:
+        dump_outputs(args.dump_outputs, rank, world, found, st)
+    # the counting pass (untimed, --full): the same K launches with the counters on
+    count_pass = args.full and not args.no_recount
+    recount = None if count_pass else found_any
+    for k in (range(args.warmup, args.warmup + args.steps) if count_pass else ()):
         found, st = step(k, 0)
         dcounts.append(st)
         if found is not None:
@@ -259,6 +274,14 @@ def main():
 
     total_evals = world * args.steps * batch * max(1, args.devices)
     value = total_evals / elapsed
+    if not args.full:
+        # a plain run ends here: the headline figure and what describes the timed launches
+        if rank == 0:
+            print(json.dumps(plain_result(args, world, value, elapsed, batch, dp, jit_s, rccl_world,
+                                          dist is not None, found_any, timed_evals, kms)), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     avg_kernel_s = sum(kms) / len(kms) / 1e3
     # executed algorithmic work per launch: every wide division priced by the
     # path each wave took (mg_stats.lane_div_*; compiler.DIV_PRICE_*), and the
@@ -354,6 +377,59 @@ def main():
     print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+def plain_result(args, world, value, elapsed, batch, dp, jit_s, rccl_world, distributed, found_any, timed_evals, kms):
+    """The result line of a run without --full: the headline fields of the full
+    line, with the same meaning, and the part of its config that the timed
+    launches alone determine."""
+    return {
+        "metric": "candidate-assignment evals/sec",
+        "value": value,
+        "unit": "evals/s",
+        "n_gpus": world * max(1, args.devices),
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u256 (u32 limbs)",
+        "data": "synthetic (Philox-generated candidates, planted witness)",
+        "config": {
+            "workload": "C5 (BASELINE.json configs[4], per-GPU shard), exhaustive search",
+            "candidates_per_gpu_step": batch,
+            "engine": args.engine + (f" ({dp.kernel})" if getattr(dp, "kernel", None) else "")
+                      + (" [host emulator: CPU test of the rank plumbing, not a measurement]"
+                         if args.host_emulator else ""),
+            "jit_compile_s": jit_s,
+            "jit_split": bool(args.jit_split) if args.engine == "jit" else None,
+            "rccl_world": rccl_world,
+            "dist_backend": args.dist_backend if distributed else None,
+            "candidate_begin": args.begin,
+            "witness_found_in_timed_range": found_any,
+            "evals_timed": timed_evals,
+            "kernel_ms_avg": sum(kms) / len(kms),
+        },
+    }
+
+
+STAT_FIELDS = ("evals", "launches", "ops", "lane_div_steps", "lane_div_full", "lane_div_short", "lane_div_general")
+
+
+def dump_outputs(path, rank, world, found, st):
+    """--dump-outputs: what the last timed search launch returned to its caller,
+    as float64 arrays.  found.npy: [1, low 32 bits, high 32 bits] of the lowest
+    satisfying index in the step's range, or [0, 0, 0] when it holds none;
+    stats.npy: the launch's counters in the order of STAT_FIELDS (its two clock
+    readings are left out: they differ from run to run).  Rank r > 0 of a
+    multi-rank run writes found_rank<r>.npy and stats_rank<r>.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 and rank else ""
+    idx = [0, 0, 0] if found is None else [1, found & 0xFFFFFFFF, found >> 32]
+    np.save(os.path.join(path, f"found{tag}.npy"), np.array(idx, dtype=np.float64))
+    np.save(os.path.join(path, f"stats{tag}.npy"), np.array([st.get(k, 0) for k in STAT_FIELDS], dtype=np.float64))
 
 
 def time_to_first_witness(dev, dp, seed, slice_log2=24, max_slices=128, dist=None, device=None, begin=0):

@@ -39,8 +39,8 @@ def test_cpu_baseline_checks_verdicts_around_the_planted_witness():
     each finds the witness (host emulator: plumbing, not a measurement)."""
     import subprocess
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--host-emulator", "--engine", "interp",
-                        "--nodes", "300", "--batch-log2", "12", "--steps", "1", "--warmup", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--host-emulator",
+                        "--engine", "interp", "--nodes", "300", "--batch-log2", "12", "--steps", "1", "--warmup", "0",
                         "--cpu-seconds", "0.5", "--no-ttfw"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

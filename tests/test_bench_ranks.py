@@ -44,7 +44,7 @@ def _run_bench(extra):
 
 def test_bench_spawns_two_ranks_and_reduces_the_minimum():
     begin = WITNESS - 300                # the planted witness falls in rank 1's slice
-    out = _run_bench(["--gpus", "2", "--begin", str(begin), "--ttfw-slice-log2", "8",
+    out = _run_bench(["--full", "--gpus", "2", "--begin", str(begin), "--ttfw-slice-log2", "8",
                       "--ttfw-max-slices", "4", "--ttfw-begin", str(WITNESS - 700)])
     assert out["n_gpus"] == 2
     assert out["config"]["rccl_world"] == 2
@@ -57,6 +57,36 @@ def test_bench_spawns_two_ranks_and_reduces_the_minimum():
     assert ttfw["index"] == _single_process_min(WITNESS - 700, 4 * (2 << 8))
     assert ttfw["candidates_searched"] == 2 * (2 << 8)
     assert out["value"] > 0 and out["scaling"] == "weak"
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full: the headline fields only, --steps timed steps, and
+    --dump-outputs holds what the last timed search returned (step k of a
+    one-rank run searches [begin + k * batch, begin + (k + 1) * batch))."""
+    import numpy as np
+    batch = 1 << BATCH_LOG2
+    begin = WITNESS - 100 - 2 * batch    # warm-up step 0, timed steps 1 and 2: the witness falls in step 2
+    args = ["--begin", str(begin), "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")]
+    out = _run_bench(args)
+    assert out["steps"] == 2 and out["config"]["evals_timed"] == 2 * batch
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["unit"] == "evals/s" and out["higher_is_better"] is True
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - batch) < 1e-6 * batch
+    for moved in ("roofline", "cpu_baseline"):
+        assert moved not in out
+    assert "time_to_first_witness" not in out["config"]
+    single = _single_process_min(begin + 2 * batch, batch)
+    assert single is not None and out["config"]["witness_found_in_timed_range"] == single
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["found.npy", "stats.npy"]
+    found = np.load(tmp_path / "out" / "found.npy")
+    assert found.dtype == np.float64 and found[0] == 1 and int(found[1]) + (int(found[2]) << 32) == single
+    stats = np.load(tmp_path / "out" / "stats.npy")
+    assert stats.dtype == np.float64 and stats[0] == batch
+    # the same arguments again: the same arrays; and a last step without a witness
+    _run_bench(args[:-1] + [str(tmp_path / "again")])
+    assert np.array_equal(np.load(tmp_path / "again" / "found.npy"), found)
+    assert np.array_equal(np.load(tmp_path / "again" / "stats.npy"), stats)
+    _run_bench(["--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "none")])
+    assert np.load(tmp_path / "none" / "found.npy").tolist() == [0.0, 0.0, 0.0]
 
 
 def test_bench_rejects_mismatched_world_size():

@@ -7,8 +7,8 @@
 #   smoke          __graft_entry__.smoke()
 #   tests[=EXPR]   pytest -m gpu (optionally -k EXPR)
 #   quick=EXPR     pytest -m gpu -k EXPR under a 180 s limit (first runs of new kernels)
-#   bench          python bench.py (default flags) -> bench.json
-#   bench1         bench.py --steps 5 --no-ttfw --no-cpu-baseline $BENCH_ARGS (quick A/B runs)
+#   bench          python bench.py --full (every leg of the benchmark) -> bench.json
+#   bench1         bench.py --full --steps 5 --no-ttfw --no-cpu-baseline $BENCH_ARGS (quick A/B runs)
 #   prof           rocprofv3 --kernel-trace --stats on a short bench run
 #   pmc            PMC passes on one bench launch (SQ, instruction mix, FETCH_SIZE, WRITE_SIZE)
 #   config         tools/config_bench.py (C2-C4 queries) -> config_bench.json
@@ -64,10 +64,10 @@ for step in "$@"; do
       run 1000 "$OUT/gpu_tests.log" python3 -u -m pytest tests -m gpu -x -v -s --timeout 150 --timeout-method thread "${K[@]}"
       tail -3 "$OUT/gpu_tests.log" ;;
     bench)
-      run 500 "$OUT/bench.err" bash -c "python3 bench.py > $OUT/bench.json"
+      run 500 "$OUT/bench.err" bash -c "python3 bench.py --full > $OUT/bench.json"
       cat "$OUT/bench.json" ;;
     bench1)
-      run 300 "$OUT/bench1.err" bash -c "${B/--no-recount/} > $OUT/bench1.json"
+      run 300 "$OUT/bench1.err" bash -c "${B/--no-recount/--full} > $OUT/bench1.json"
       cat "$OUT/bench1.json" ;;
     prof)
       run 400 "$OUT/prof.log" rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- $B
