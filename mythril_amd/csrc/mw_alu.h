@@ -613,6 +613,85 @@ MW_HD void udivrem8(const u32 x[8], const u32 y[8], u32 q[8], u32 r[8], DivCount
   copy8(r, u);
 }
 
+// udivrem8 for operands with static limb bounds: the caller promises
+// x < 2^(32 NX) and y < 2^(32 NY) (jit.py value_bounds: the program's own
+// structure, e.g. a masked word or a 160-bit address in a 256-bit term).
+// When every lane's divisor has exactly NY limbs, udivrem8 would take the same
+// path in every wave, with the alignment n = 8 - NY in every lane; here that
+// path is chosen at compile time:
+//   NY == 8 (NX < 8): x < y, so q = 0 and r = x: no estimate, no multiply;
+//   NY == 1: short division;
+//   otherwise the limb-aligned schoolbook division on unshifted operands: no
+//     select stages, max(0, NX - NY + 1) digit positions, unrolled, each a
+//     multiply-subtract over NY + 1 limbs behind udivrem8's wave test.  The
+//     positions above NX - NY have an all-zero window top in udivrem8 and
+//     never pass its test, so the windows that do run are the same ones.
+// The guard makes the promise harmless and the path exact: a wave with a limb
+// at or above a bound nonzero, or with a lane whose divisor is narrower than
+// NY limbs, runs udivrem8.  *dc receives what udivrem8 counts for the wave.
+template <int NX, int NY>
+MW_HD void udivrem8_nb(const u32 x[8], const u32 y[8], u32 q[8], u32 r[8], DivCount* dc = nullptr) {
+  static_assert(NX >= 0 && NX <= 8 && NY >= 1 && NY <= 8, "limb bounds");
+  u32 over = 0u;
+#pragma unroll
+  for (int k = NX; k < 8; ++k) over |= x[k];
+#pragma unroll
+  for (int k = NY; k < 8; ++k) over |= y[k];
+  if (MW_RARE(MW_ANY(over != 0u || y[NY - 1] == 0u))) {
+    udivrem8(x, y, q, r, dc);
+    return;
+  }
+  if (NY == 8) {  // x < 2^224 <= y
+    if (dc) dc->full += 1u;
+    zero8(q);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[k] = k < NX ? x[k] : 0u;
+    return;
+  }
+  if (NY == 1) {
+    u32 xs[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) xs[k] = k < NX ? x[k] : 0u;
+    udivrem8_short(xs, y[0], q, r);
+    if (dc) dc->shrt += 1u;
+    return;
+  }
+  if (dc) dc->gen += 1u;
+  constexpr int D = NY < 2 ? 2 : (NY > 7 ? 7 : NY);  // divisor limbs on this path (2..7)
+  u32 u[10];  // the remainder in place: limbs 0..NX-1 of x, zero above
+#pragma unroll
+  for (int k = 0; k < 10; ++k) u[k] = k < NX ? x[k] : 0u;
+  zero8(q);
+#pragma unroll
+  for (int j = NX - D; j >= 0; --j) {  // digit position j: the window u[j .. j+D]
+    if (MW_ANY(u[j + D] != 0u || u[j + D - 1] >= y[D - 1])) {  // else digit 0 in every lane
+      if (dc) dc->steps += 1u;
+      u32 qd = qdigit_est3(u[j + D], u[j + D - 1], u[j + D - 2], y[D - 1], y[D - 2]);
+      u32 carry = 0, br = 0;
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        const u64 p = (u64)qd * y[k] + carry;
+        carry = (u32)(p >> 32);
+        u[j + k] = subb(u[j + k], (u32)p, br);
+      }
+      u32 hi = u[j + D] - carry - br;  // 0, or the negative top limb when qd is too large
+      while (MW_RARE(MW_ANY(hi != 0u))) {
+        if (hi != 0u) {
+          u32 c = 0;
+#pragma unroll
+          for (int k = 0; k < D; ++k) u[j + k] = addc(u[j + k], y[k], c);
+          hi += c;
+          qd -= 1u;
+        }
+      }
+      u[j + D] = 0u;
+      q[j] = qd;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) r[k] = k < D ? u[k] : 0u;
+}
+
 MW_HD void neg8(const u32 a[8], u32 r[8]) {
   u32 br = 0;
 #pragma unroll
@@ -669,6 +748,62 @@ MW_HD void wdiv(int kind, u32 x[8], u32 y[8], u32 w, u32 r[8], DivCount* dc = nu
       // sa & !sb : t - u ; !sa & sb : u + t ; sa & sb : -u
       const bool negu = sa;
       cneg8(r, negu, w);  // r = sa ? -u : u
+      const bool addt = !uz && (sa != sb);
+      u32 c = 0;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const u32 t = addc(r[k], y[k], c);
+        r[k] = addt ? t : r[k];
+      }
+      break;
+    }
+  }
+  canon(r, w);
+}
+
+// wdiv over udivrem8_nb: the caller promises x < 2^(32 NX) and y < 2^(32 NY) for
+// the w-bit operands as given.  The magnitudes keep the bounds: a bound below w
+// bits means the sign bit is clear, and |s| <= 2^(w-1) fits any bound of w bits
+// or more.  A zero divisor becomes 1 as in wdiv (for NY > 1 its limb NY - 1 is
+// then zero, so the wave takes udivrem8_nb's fallback).
+template <int NX, int NY>
+MW_HD void wdiv_nb(int kind, u32 x[8], u32 y[8], u32 w, u32 r[8], DivCount* dc = nullptr) {
+  bool sa = false, sb = false;
+  if (kind >= 2) {
+    sa = signbit8(x, w);
+    sb = signbit8(y, w);
+    cneg8(x, sa, w);
+    cneg8(y, sb, w);
+  }
+  const bool yz = is_zero8(y);
+  y[0] |= yz ? 1u : 0u;
+  u32 q[8];
+  udivrem8_nb<NX, NY>(x, y, q, r, dc);
+  if (yz) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      q[k] = limb_mask(w, k);
+      r[k] = x[k];
+    }
+  }
+  switch (kind) {
+    case 0:
+      copy8(r, q);
+      break;
+    case 1:
+      break;
+    case 2:
+      copy8(r, q);
+      cneg8(r, sa != sb, w);
+      break;
+    case 3:
+      cneg8(r, sa, w);
+      break;
+    default: {  // smod, as in wdiv
+      const bool uz = is_zero8(r);
+      if (yz) y[0] = 0u;
+      cneg8(y, sb, w);
+      cneg8(r, sa, w);
       const bool addt = !uz && (sa != sb);
       u32 c = 0;
 #pragma unroll

@@ -80,6 +80,12 @@ LDS_AHEAD_STOP = int(os.environ.get("MW_JIT_LDS_AHEAD_STOP", "500"))
 # lines -0.5 / -0.8 / -1.0 / -1.5 / -2.1 / -2.3 %, with the unreused kernel's
 # spills up to 96 lines (12 bytes per lane) and 68 bytes at 192: 96
 LDS_REUSE = int(os.environ.get("MW_JIT_LDS_REUSE", "96"))
+# Wide divisions and register x register products whose operands have a static
+# bound below 8 limbs (value_bounds) call the range-specialised helpers
+# (mw_jit.h w_div_nb / w_mul_nb); "0" emits the source without them, line for line
+RANGES = os.environ.get("MW_JIT_RANGES", "1") != "0"
+# experiments (tools/ab_c5.py "ranges_div"): the divisions only
+RANGES_MUL = True
 M32 = 0xFFFFFFFF
 
 _WBIN = {"W_ADD": "w_add", "W_SUB": "w_sub", "W_MUL": "w_mul", "W_AND": "w_and", "W_OR": "w_or",
@@ -169,15 +175,129 @@ def interleave_conjuncts(insns: List[MInsn], k: int) -> List[MInsn]:
     return out + tail
 
 
+def value_bounds(insns: Sequence[MInsn], p: Optional[Program] = None) -> Dict[int, int]:
+    """Forward range pass over SSA machine IR: for every wide register an upper
+    bound b on its significant bits (value < 2^b in every candidate), from the
+    program's own structure: masks, shifts by constants, extensions, narrow
+    leaves.  Every result is clamped by its instruction's width; an op without
+    a rule (W_SUB, W_NOT, sign extensions, ...) gets its width.  Narrow
+    registers count as 32 bits.
+
+    A quotient is bounded by its dividend, and a remainder also by its divisor,
+    only where the divisor cannot be zero (a nonzero constant, or an OR with
+    one, as in `x | 1`): SMT-LIB's x / 0 is all ones and x % 0 is x."""
+    b: Dict[int, int] = {}
+    nz: set = set()    # registers that are nonzero in every candidate
+
+    def bound(s, width):
+        if isinstance(s, Const):
+            return (s.value & M256).bit_length()
+        if s.cls != "W":
+            return 32
+        return b.get(s.id, width if 0 < width <= 256 else 256)
+
+    def nonzero(s, width):
+        if isinstance(s, Const):
+            return (s.value & ((1 << width) - 1)) != 0
+        return s.id in nz
+
+    for ins in insns:
+        d = ins.dst
+        if d is None or d.cls != "W":
+            continue
+        op, S = ins.op, ins.srcs
+        w = ins.width if 0 < ins.width <= 256 else 256
+        B = [bound(s, w) for s in S]
+        r = w
+        if op == "LEAF_W" and p is not None:
+            r = int(p.leaves[ins.imm * isa.LEAF_WORDS])      # the leaf's width
+        elif op == "MOV_W":
+            r = B[0]
+            if B[0] <= w and nonzero(S[0], w):
+                nz.add(d.id)
+        elif op == "W_AND":
+            r = min(B)
+        elif op in ("W_OR", "W_XOR"):
+            r = max(B)
+            if op == "W_OR" and any(bb <= w and nonzero(s, w) for s, bb in zip(S, B)):
+                nz.add(d.id)
+        elif op == "W_ADD":
+            r = max(B) + 1
+        elif op == "W_MUL":
+            r = 0 if 0 in B else B[0] + B[1]
+        elif op == "W_SHLI":
+            r = B[0] + ins.imm if B[0] else 0
+        elif op == "W_LSHRI":
+            r = max(B[0] - ins.imm, 0)
+        elif op == "W_LSHR":
+            r = B[0]
+        elif op == "W_ASHR":
+            r = B[0] if B[0] < w else w       # sign bit clear: a logical shift
+        elif op == "W_ITE":
+            r = max(B[0], B[1])
+            if all(bb <= w and nonzero(s, w) for s, bb in zip(S[:2], B[:2])):
+                nz.add(d.id)
+        elif op == "W_ZEXTN":
+            r = 32
+        elif op == "W_INSN":
+            r = max(B[0], ins.imm + 32)
+        elif op in ("W_UDIV", "W_UREM", "W_SDIV", "W_SREM", "W_SMOD"):
+            unsigned = op in ("W_UDIV", "W_UREM") or (B[0] < w and B[1] < w)   # both sign bits clear
+            if not unsigned:
+                r = w
+            elif op in ("W_UDIV", "W_SDIV"):
+                r = B[0] if nonzero(S[1], w) else w
+            else:
+                r = min(B[0], B[1]) if nonzero(S[1], w) else B[0]
+        b[d.id] = max(0, min(r, w))
+    return b
+
+
+def _limbs(bits: int) -> int:
+    return (bits + 31) // 32
+
+
+def _site_bounds(ins: MInsn, bounds: Dict[int, int]) -> Tuple[int, int]:
+    """Static limb bounds of a two-operand wide instruction's operands."""
+    w = ins.width if 0 < ins.width <= 256 else 256
+    out = []
+    for s in ins.srcs[:2]:
+        bits = (s.value & M256).bit_length() if isinstance(s, Const) else bounds.get(s.id, w)
+        out.append(_limbs(min(bits, w)))
+    return out[0], out[1]
+
+
+def range_sites(p: Program, insns: Optional[Sequence[MInsn]] = None) -> Dict[str, Dict[Tuple[int, int], int]]:
+    """Per class of static limb bounds, the number of wide divisions ("div":
+    (dividend, divisor)) and of register x register products ("mul") of a
+    program (DESIGN.md, "Operand ranges")."""
+    insns = p.machine_ir() if insns is None else insns
+    bounds = value_bounds(insns, p)
+    out: Dict[str, Dict[Tuple[int, int], int]] = {"div": {}, "mul": {}}
+    for ins in insns:
+        if ins.op.startswith("W_") and ins.op[2:] in _DIV:
+            nx, ny = _site_bounds(ins, bounds)
+            key, kind = (nx, max(ny, 1)), "div"
+        elif ins.op == "W_MUL" and all(isinstance(s, VReg) for s in ins.srcs):
+            key, kind = _site_bounds(ins, bounds), "mul"
+        else:
+            continue
+        out[kind][key] = out[kind].get(key, 0) + 1
+    return out
+
+
 class _Gen:
     """Emit the body of one program as straight-line HIP."""
 
     def __init__(self, p: Program, name: str, fence_first: bool = False, lds_leaves: int = 0,
-                 insns: Optional[List[MInsn]] = None, interleave: int = 1, mul_cols: Optional[bool] = None):
+                 insns: Optional[List[MInsn]] = None, interleave: int = 1, mul_cols: Optional[bool] = None,
+                 ranges: Optional[bool] = None):
         self.fence_first = fence_first  # diagnostics (tools/opbench.py): no folding across nodes
         self.mul_cols = MUL_COLS if mul_cols is None else mul_cols
         self.p = p
         self.insns = interleave_conjuncts(p.machine_ir() if insns is None else insns, interleave)
+        # static bit bounds of the wide values (None: the range-specialised helpers are off)
+        self.bounds = value_bounds(self.insns, p) if (RANGES if ranges is None else ranges) else None
         # the lds_leaves most-used wide leaves live in LDS (mw_jit.h lds_put8/lds_get8)
         uses: Dict[int, int] = {}
         defs: Dict[int, int] = {}
@@ -296,11 +416,17 @@ class _Gen:
         elif op == "MOV_N":
             out(f"const u32 {dn} = {A[0]};")
         elif op == "W_MUL" and self.mul_cols and all(isinstance(s, VReg) for s in S):
-            out(f"u32 {dn}[8]; jit::w_mulv({A[0]}, {A[1]}, {w}u, {dn});")
+            na, nb = _site_bounds(ins, self.bounds) if self.bounds is not None and RANGES_MUL else (8, 8)
+            if min(na, nb) < 8:
+                out(f"u32 {dn}[8]; jit::w_mul_nb<{na}, {nb}>({A[0]}, {A[1]}, {w}u, {dn});")
+            else:
+                out(f"u32 {dn}[8]; jit::w_mulv({A[0]}, {A[1]}, {w}u, {dn});")
         elif op in _WBIN:
             out(f"u32 {dn}[8]; jit::{_WBIN[op]}({A[0]}, {A[1]}, {w}u, {dn});")
         elif op.startswith("W_") and op[2:] in _DIV:
-            out(f"u32 {dn}[8]; jit::w_div({_DIV[op[2:]]}, {A[0]}, {A[1]}, {w}u, {dn}, dsteps);")
+            nx, ny = _site_bounds(ins, self.bounds) if self.bounds is not None else (8, 8)
+            nb = f"_nb<{nx}, {max(ny, 1)}>" if min(nx, ny) < 8 else ""
+            out(f"u32 {dn}[8]; jit::w_div{nb}({_DIV[op[2:]]}, {A[0]}, {A[1]}, {w}u, {dn}, dsteps);")
         elif op == "W_NOT":
             out(f"u32 {dn}[8]; jit::w_not({A[0]}, {w}u, {dn});")
         elif op == "W_ITE":
@@ -479,7 +605,7 @@ def split_ssa(p: Program, part_weight: int = PART_WEIGHT) -> List[List[MInsn]]:
 def generate(progs: Sequence[Program], names: Sequence[str], variants: str = "xe",
              fence_first: bool = False, lds_leaves: int = 0,
              parts: Optional[Sequence[Tuple[List[MInsn], int, int]]] = None, interleave: int = 1,
-             mul_cols: Optional[bool] = None) -> str:
+             mul_cols: Optional[bool] = None, ranges: Optional[bool] = None) -> str:
     """HIP source for a module holding one specialised kernel set per program
     (with `parts`: per program, its (instructions, part index, part count))."""
     out = ["// generated by mythril_amd/jit.py: specialised witness-search kernels"]
@@ -505,7 +631,7 @@ def generate(progs: Sequence[Program], names: Sequence[str], variants: str = "xe
         part = parts[k] if parts else None
         out.append(f"// program {name}: {p.n_insn} bytecode insns, {p.ops_per_eval} u32 ops/eval"
                    + (f", part {part[1]} of {part[2]}" if part else ""))
-        out.append(_Gen(p, name, fence_first, lds_leaves, part[0] if part else None, interleave, mul_cols).body())
+        out.append(_Gen(p, name, fence_first, lds_leaves, part[0] if part else None, interleave, mul_cols, ranges).body())
         out.append(f"MW_JIT_SIG({name}, {signature(p):#x}ull)")
         if part:
             out.append(f"MW_JIT_PART({name}, {part[1]}u, {part[2]}u)")

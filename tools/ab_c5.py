@@ -78,7 +78,13 @@ VARIANTS = {"base": {"EXTRA_FLAGS": []},
             "reuse96": {"EXTRA_FLAGS": [], "LDS_REUSE": 96}, "reuse192": {"EXTRA_FLAGS": [], "LDS_REUSE": 192},
             "reuse128": {"EXTRA_FLAGS": [], "LDS_REUSE": 128},
             "l8r96": {"EXTRA_FLAGS": [], "LDS_REUSE": 96, "lds": 8},
-            "a32r96": {"EXTRA_FLAGS": [], "LDS_REUSE": 96, "LDS_AHEAD": 32}}
+            "a32r96": {"EXTRA_FLAGS": [], "LDS_REUSE": 96, "LDS_AHEAD": 32},
+            # divisions and products specialised by static operand ranges (jit.RANGES): on, off
+            # (the source without them, line for line), and the divisions alone
+            "ranges": {"EXTRA_FLAGS": [], "RANGES": True}, "noranges": {"EXTRA_FLAGS": [], "RANGES": False},
+            # the same kernel as "noranges" under a second name: the spread of repeated runs
+            "noranges2": {"EXTRA_FLAGS": [], "RANGES": False},
+            "ranges_div": {"EXTRA_FLAGS": [], "RANGES": True, "RANGES_MUL": False}}
 
 
 MUL_COLS_DEFAULT = jit.MUL_COLS
@@ -87,6 +93,7 @@ LDS_AHEAD_W_DEFAULT = jit.LDS_AHEAD_W
 LDS_AHEAD_STOP_DEFAULT = jit.LDS_AHEAD_STOP
 SPLIT_EVERY_DEFAULT = jit.SPLIT_EVERY
 LDS_REUSE_DEFAULT = jit.LDS_REUSE
+RANGES_DEFAULT = jit.RANGES
 
 
 def main():
@@ -101,7 +108,7 @@ def main():
     p = compile_program(syn.conjuncts)
     images = {}
     for v in a.variants.split(","):
-        opts = {"CHECK_SYNC": False, "CHECK_SYNC_EVERY": 1, "LDS_REUSE": LDS_REUSE_DEFAULT, "MUL_COLS": MUL_COLS_DEFAULT, "LDS_AHEAD": LDS_AHEAD_DEFAULT, "LDS_AHEAD_W": LDS_AHEAD_W_DEFAULT,
+        opts = {"RANGES": RANGES_DEFAULT, "RANGES_MUL": True, "CHECK_SYNC": False, "CHECK_SYNC_EVERY": 1, "LDS_REUSE": LDS_REUSE_DEFAULT, "MUL_COLS": MUL_COLS_DEFAULT, "LDS_AHEAD": LDS_AHEAD_DEFAULT, "LDS_AHEAD_W": LDS_AHEAD_W_DEFAULT,
                 "LDS_AHEAD_STOP": LDS_AHEAD_STOP_DEFAULT, "SPLIT_EVERY": SPLIT_EVERY_DEFAULT, **VARIANTS[v]}
         il = opts.pop("interleave", 1)
         waves, lds = opts.pop("waves", 2), opts.pop("lds", 10)

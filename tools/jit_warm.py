@@ -44,8 +44,14 @@ def main():
             print("tests/test_gpu_jit.py mul_cols=%s:" % cols,
                   jit.compile_device(mul_check_programs(), mul_cols=cols)[2], "s", flush=True)
 
+    def ranges():
+        from tests.test_gpu_jit_ranges import range_test_programs
+        print("tests/test_gpu_jit_ranges.py module:", jit.compile_device(range_test_programs())[2], "s", flush=True)
+
     from config_bench import warm_jobs as config_jobs   # tools/config_bench.py (C2-C4 solver-log queries)
     jobs += config_jobs() + [gpu_jit_modules, constant_divisors, mul_cols]
+    if jit.RANGES:   # otherwise after the pool: that module is built with the switch on
+        jobs.append(ranges)
     if "--opbench" in sys.argv:
         from opbench import OPS, chain
 
@@ -57,6 +63,10 @@ def main():
     with ThreadPoolExecutor(workers) as ex:
         for f in [ex.submit(j) for j in jobs]:
             f.result()   # re-raise the first failure
+    if not jit.RANGES:
+        jit.RANGES = True
+        ranges()
+        jit.RANGES = False
     print(f"jit warm-up: {len(jobs)} jobs on {workers} workers in {time.perf_counter() - t0:.0f} s", flush=True)
     if "--prune" in sys.argv:
         print("pruned", jit.prune_cache(), "stale cache entries", flush=True)
