@@ -717,14 +717,16 @@ def is_cached(progs: Sequence[Program], variants: str = "xe", waves: int = 2, ld
 
 def compile_device(progs: Sequence[Program], variants: str = "xe", fence_first: bool = False,
                    waves: int = 2, lds_leaves: int = 0, interleave: int = 1,
-                   mul_cols: Optional[bool] = None) -> Tuple[bytes, List[str], float]:
+                   mul_cols: Optional[bool] = None, ranges: Optional[bool] = None) -> Tuple[bytes, List[str], float]:
     """gfx950 code object for `progs`; returns (image, kernel names, compile seconds; 0 if cached).
+    ranges: the range pass on or off for this module (None: the RANGES switch).
 
     waves: waves per SIMD the kernels are built for (launch bounds): 2 gives
     each lane 256 registers, 1 gives 512 (AGPRs become spill space instead of
     scratch memory) at half the latency hiding."""
     names = [kernel_name(p) for p in progs]
-    src = generate(progs, names, variants, fence_first, lds_leaves, interleave=interleave, mul_cols=mul_cols)
+    src = generate(progs, names, variants, fence_first, lds_leaves, interleave=interleave, mul_cols=mul_cols,
+                   ranges=ranges)
     path, dt = _compile(src, _device_flags(waves), ".hsaco", ".hip")
     return path.read_bytes(), names, dt
 

@@ -197,12 +197,27 @@ def test_invalid_program_rejected(dev):
 
 
 def test_division_rare_paths_gpu(dev):
+    """The unsigned programs run on the asm interpreter (its bit-serial
+    divider), the signed ones on the compiled interpreter (udivrem8), per
+    isa.asm_eligible; every program a second time on the compiled interpreter."""
     from tests.helpers import division_check_programs
-    for p in division_check_programs():
+    from tests.test_gpu_asm import compiled_interpreter
+    progs = division_check_programs()
+    assert len(progs) == 5
+    for k, p in enumerate(progs):   # bvudiv, bvurem, bvsdiv, bvsrem, bvsmod
+        engine = "asm" if k < 2 else "interp"
+        assert isa.asm_eligible(p.code, p.leaves, p.consts) == (engine == "asm")
         dp = dev.load(p)
-        v, _ = dev.eval_generated(dp, 1, 0, 256, trace=False)
-        assert int(v.sum()) == 256
-        dp.free()
+        try:
+            assert dev.engine_of(dp) == engine
+            v, _ = dev.eval_generated(dp, 1, 0, 256, trace=False)
+            assert int(v.sum()) == 256
+            with compiled_interpreter():
+                assert dev.engine_of(dp) == "interp"
+                v, _ = dev.eval_generated(dp, 1, 0, 256, trace=False)
+                assert int(v.sum()) == 256, f"compiled interpreter, program {k}"
+        finally:
+            dp.free()
 
 
 def test_keccak_service_on_device(dev):

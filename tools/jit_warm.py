@@ -48,8 +48,14 @@ def main():
         from tests.test_gpu_jit_ranges import range_test_programs
         print("tests/test_gpu_jit_ranges.py module:", jit.compile_device(range_test_programs())[2], "s", flush=True)
 
+    def opmatrix(ranges):
+        from tests.opmatrix import jit_programs
+        print("tests/test_gpu_opmatrix.py module ranges=%s:" % ranges,
+              jit.compile_device(jit_programs(), variants="x", ranges=ranges)[2], "s", flush=True)
+
     from config_bench import warm_jobs as config_jobs   # tools/config_bench.py (C2-C4 solver-log queries)
     jobs += config_jobs() + [gpu_jit_modules, constant_divisors, mul_cols]
+    jobs += [lambda: opmatrix(True), lambda: opmatrix(False)]
     if jit.RANGES:   # otherwise after the pool: that module is built with the switch on
         jobs.append(ranges)
     if "--opbench" in sys.argv:
