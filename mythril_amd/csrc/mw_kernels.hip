@@ -30,6 +30,7 @@
 #include "mw_inflight.h"
 #include "mw_interp.h"
 #include "mw_keccak.h"
+#include "mw_launch_plan.h"
 #include "mw_leaf.h"
 
 extern "C" int mw_fail(int code, const char* msg);
@@ -44,17 +45,10 @@ using namespace mw;
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kNCounters = 5;  // counter words: evals, then DivCount fields x lanes
 // d_counter: stripe 0 (interpreters) + MW_CTR_STRIPES stripes (specialised kernels), summed on readback
 constexpr size_t kCounterWords = (size_t)(1 + MW_CTR_STRIPES) * MW_CTR_STRIPE_WORDS;
-// Spill area: n_spill words per lane (a W spill slot is 8 consecutive words, an
-// N slot one; the compiler puts the most-used words first).  Words
-// [0, kLdsSpillWords) live in LDS as [word][lane] (consecutive lanes ->
-// consecutive banks): 80 words = 80 KiB per 256-lane block, so two blocks (8
-// waves) still fit a CU's 160 KiB; the rest in the global spill buffer,
-// [word][thread].
-constexpr u32 kLdsSpillWords = 80;
+// the spill area's LDS part (mw_launch_plan.h kLdsSpillWords), then a staged pool
 extern __shared__ u32 lds_spill[];
 
 typedef const __attribute__((address_space(3))) u32* lptr;
@@ -289,9 +283,7 @@ __global__ __launch_bounds__(kBlock, 4) void mw_search_asm_kernel_q(const ProgDe
   MW_ASM_KERNEL_BODY_C(MW_ASM_BODY_Q, lds_spill, MW_ASM_CLOBBERS_Q)
 }
 
-// the asm interpreter's kernels by register layout (Prog::asm_layout)
-typedef uint8_t u8;
-enum AsmLayout : u8 { kWide = 0, kNarrow = 1, kQuarter = 2, kAsmLayouts = 3 };
+// the asm interpreter's kernels by register layout (mw_launch_plan.h AsmLayout)
 typedef void (*AsmKernel)(const ProgDev*, const AsmArgs*, u64*, u64*, u32);
 const AsmKernel kAsmKernel[kAsmLayouts] = {mw_search_asm_kernel, mw_search_asm_kernel_n, mw_search_asm_kernel_q};
 
@@ -420,12 +412,9 @@ struct Prog;
 struct Pending {
   bool active = false;
   std::vector<std::shared_ptr<Prog>> ps;   // the programs, alive until the end
-  std::vector<size_t> slot;                // program i's word in d_min
-  std::vector<size_t> interp, special;     // d_min order (search_complete)
-  size_t nia = 0;
-  u64 count = 0, ops = 0, seed = 0;
+  SearchPlan plan;                         // what was launched: d_min order, launch count, ops
+  u64 count = 0, seed = 0;
   u32 flags = 0;
-  size_t nlaunches = 0;
   double t0 = 0.0;
   bool gpu_steps = false;
 };
@@ -825,14 +814,20 @@ hipError_t stage_readback(Ctx* c, size_t nmin) {
   return hipMemcpyAsync(c->h_blk, c->d_blk, c->off_min + nmin * sizeof(u64), hipMemcpyDeviceToHost, c->stream);
 }
 
-// One launch of a program's assembled kernel: the asm interpreter's grid (x:
-// chunk stride, one program) and records (mw_asm_abi.h); its LDS is a fixed
-// 80 KiB array in the kernel (mw_asmjit_shell.hip).
-int launch_assembled(Ctx* c, const Prog* p, u32 gx, const ProgDev* dprog, const AsmArgs* dargs, u64* dmin,
-                     u32 nlds) {
-  u64* ctr = c->d_counter;
-  void* args[] = {&dprog, &dargs, &dmin, &ctr, &nlds};
-  HIPCHK(hipModuleLaunchKernel(p->afn, gx, 1, 1, kBlock, 1, 1, 0, c->stream, args, nullptr));
+// One launch of an asm engine over gx blocks on the records at dprog and dargs
+// (mw_asm_abi.h): a program's assembled kernel afn, whose LDS is a fixed 80 KiB
+// array in the kernel (mw_asmjit_shell.hip), or with afn null the interpreter
+// kernel of `layout`, its dynamic LDS nlds spill rows and a pool of npool words.
+int launch_asm(Ctx* c, hipFunction_t afn, u8 layout, const ProgDev* dprog, const AsmArgs* dargs, u64* dmin,
+               u64* counter, u64 gx, u32 nlds, u32 npool) {
+  if (afn) {
+    void* args[] = {&dprog, &dargs, &dmin, &counter, &nlds};
+    HIPCHK(hipModuleLaunchKernel(afn, (u32)gx, 1, 1, kBlock, 1, 1, 0, c->stream, args, nullptr));
+    return 0;
+  }
+  hipLaunchKernelGGL(kAsmKernel[layout], dim3((u32)gx, 1u), dim3(kBlock), asm_lds_bytes(nlds, npool), c->stream, dprog,
+                     dargs, dmin, counter, nlds);
+  HIPCHK(hipGetLastError());
   return 0;
 }
 
@@ -870,14 +865,6 @@ bool asm_eligible(const mg_prog_desc* d) {
   return true;
 }
 
-// LDS words of spill area for an asm launch whose largest pool has max_pool
-// words: the pool is staged whole in LDS, the hottest spill words take what is
-// left of the block's 80 KiB and the rest spill to the global buffer.  False if
-// the pool alone does not fit (the programs then run on the compiled interpreter).
-// The narrow-layout kernel's budget: 52 KiB per block, so three blocks (three
-// waves per SIMD) fit a CU's 160 KiB; the quarter layout's 40 KiB (four).
-constexpr u32 kLdsSpillWordsByLayout[kAsmLayouts] = {kLdsSpillWords, 52, 40};
-
 // MYTHRIL_AMD_ASM_WIDE_LDS=n (81..160): the wide kernel's budget in words (A/B
 // runs: a program that spills past 80 words keeps them in LDS at one block,
 // one wave per SIMD, instead of two with the rest in global memory)
@@ -890,24 +877,20 @@ u32 wide_lds_words() {
   return w;
 }
 
-bool asm_lds_fit(u32 max_spill, u32 max_pool, u32* nlds, u8 layout = kWide, bool interp = false) {
-  const u32 words = layout == kWide && interp ? wide_lds_words() : kLdsSpillWordsByLayout[layout];
-  const size_t budget = (size_t)words * kBlock * 4, pool_bytes = (size_t)max_pool * 4;
-  if (pool_bytes > budget) return false;
-  const u32 pool_words_lds = (u32)((pool_bytes + kBlock * 4 - 1) / (kBlock * 4));  // in spill-word rows
-  *nlds = std::min(max_spill, words - pool_words_lds);
-  return true;
-}
-
-bool asm_lds_fit(const Prog* p, u32* nlds) {
-  return asm_lds_fit(p->dev.n_spill, p->dev.npool, nlds, p->asm_layout, true);
-}
-
 // MYTHRIL_AMD_ASM=0 keeps every program on the compiled interpreter (A/B runs, tests)
 bool asm_enabled() {
   const char* e = std::getenv("MYTHRIL_AMD_ASM");
   return !(e && e[0] == '0');
 }
+
+// what the launch plan reads of a loaded program (mw_launch_plan.h)
+ProgFacts facts_of(const Prog* p) {
+  return {p->dev.n_spill, p->dev.npool,  p->dev.n_insn,     p->ops_per_eval,
+          p->asm_ok,      p->asm_layout, p->afn != nullptr, p->jit_ready()};
+}
+
+// the engine a search of `count` candidates gives this program (engine_of)
+Engine prog_engine(const Prog* p, u64 count) { return engine_of(facts_of(p), asm_enabled(), count, wide_lds_words()); }
 
 // MYTHRIL_AMD_ASM_NARROW=0 predecodes every asm program for the wide kernel,
 // MYTHRIL_AMD_ASM_QUARTER=0 keeps programs off the quarter layout (A/B runs)
@@ -947,8 +930,7 @@ int introspect(K kernel, hipStream_t stream, u32* hout) {
   u32* dout = (u32*)(b + sizeof(ProgDev) + sizeof(AsmArgs));
   u64* dmin = (u64*)(dout + MW_ASM_NHTAB + (MW_ASM_NHTAB & 1));
   ProgDev hp{};
-  AsmArgs ha{};
-  ha.flags = 1u << 7;
+  AsmArgs ha = asm_args<AsmArgs>(0, 0, 0, 1u << 7, 0, 0, 0, nullptr);
   ha.verdict = dout;
   hipError_t e = hipMemsetAsync(buf, 0, bytes, stream);
   if (e == hipSuccess) e = hipMemcpyAsync(dp, &hp, sizeof hp, hipMemcpyHostToDevice, stream);
@@ -1166,12 +1148,14 @@ static int load_locked(const std::shared_ptr<Ctx>& cref, const mg_prog_desc* d, 
     // (four waves per SIMD), else the narrow one (three), else the wide one.
     // More distinct narrow constants than MW_ASM_NK: the compiled interpreter runs it
     u32 nl0 = 0;
-    if (asm_quarter_enabled() && asm_lds_fit(d->n_spill, (u32)d->npool_words, &nl0, kQuarter) &&
+    if (asm_quarter_enabled() &&
+        asm_lds_fit(d->n_spill, (u32)d->npool_words, kLdsSpillWordsByLayout[kQuarter], &nl0) &&
         nl0 == d->n_spill &&
         mw_asm_predecode_layout(d->code, nc, d->consts, d->nconst_words, g_hoff_q[c->dev], pre, pre + nc + 8,
                                 MW_ASM_NK_INDEX_Q, MW_ASM_NK_Q, MW_ASM_NFILE_Q, MW_ASM_WFILE_Q) == 0) {
       layout = kQuarter;
-    } else if (asm_narrow_enabled() && asm_lds_fit(d->n_spill, (u32)d->npool_words, &nl0, kNarrow) &&
+    } else if (asm_narrow_enabled() &&
+               asm_lds_fit(d->n_spill, (u32)d->npool_words, kLdsSpillWordsByLayout[kNarrow], &nl0) &&
                (std::memset(pre, 0, (nc + 8 + MW_ASM_NK) * 4),
                 mw_asm_predecode_layout(d->code, nc, d->consts, d->nconst_words, g_hoff_n[c->dev], pre,
                                         pre + nc + 8, MW_ASM_NK_INDEX_N, MW_ASM_NK_N, MW_ASM_NFILE_N, 0) == 0)) {
@@ -1318,11 +1302,9 @@ int mg_prog_has_kernel(const mg_prog* h) {
 int mg_prog_engine(const mg_prog* h) {
   CallG call;
   if (const char* why = mw::enter_prog(g_reg, hid(h), call)) return fail(MG_E_ARG, std::string("mg_prog_engine: ") + why);
-  const Prog* p = call.ps[0].get();
-  if (p->jit_ready()) return 2;
-  u32 nlds = 0;   // the engine mg_search gives this program alone (a pool too big for LDS: compiled)
-  if (!p->asm_ok || !asm_enabled() || !asm_lds_fit(p, &nlds)) return 0;
-  return p->afn ? 3 : 1;
+  // the engine mg_search gives this program alone (a pool too big for LDS:
+  // compiled), over a range the asm engines take (below 2^40 candidates)
+  return (int)prog_engine(call.ps[0].get(), 1).kind;
 }
 
 int mg_prog_attach_asm(mg_prog* h, const void* image, size_t size, const char* name) {
@@ -1383,153 +1365,70 @@ static bool ensure_readback(Ctx* c, size_t bytes) {
   return true;
 }
 
+// The tail of an evaluation whose launches went out with status e: read back
+// vb bytes of verdicts and the tb bytes of trace rows behind them in the same
+// device block, in one copy through the pinned buffer when they fit there
+// (else one copy each, straight to the caller's memory), and wait for the
+// stream.  Returns the first error.
+static hipError_t eval_readback(Ctx* c, hipError_t e, const char* step, const u32* d_v, size_t vb, size_t tb,
+                                uint32_t* verdict, uint32_t* trace) {
+  const bool pinned = vb + tb <= kReadbackMax && ensure_readback(c, vb + tb);
+  if (e == hipSuccess && pinned) {
+    e = hipMemcpyAsync(c->h_rb, d_v, vb + tb, hipMemcpyDeviceToHost, c->stream);
+  } else {
+    if (e == hipSuccess) e = hipMemcpyAsync(verdict, d_v, vb, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && tb) e = hipMemcpyAsync(trace, d_v + vb / 4, tb, hipMemcpyDeviceToHost, c->stream);
+  }
+  mw::inflight_step(step, vb / 4);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return e;
+  c->uploads_landed();   // the stream drained: a queued program upload has landed
+  if (pinned) {
+    std::memcpy(verdict, c->h_rb, vb);
+    if (tb) std::memcpy(trace, c->h_rb + vb, tb);
+  }
+  return hipSuccess;
+}
+
 // Plan and enqueue a search of ps (the context's mu held): the launch
 // records upload, the kernels, the readback of counters and d_min; P gets what
-// search_complete needs.  Nothing here waits for the device.
+// search_complete needs.  Nothing here waits for the device.  What is launched
+// is plan_search's decision (mw_launch_plan.h); this turns it into records
+// and launches.
 static int search_enqueue(Ctx* c, const std::vector<std::shared_ptr<Prog>>& ps, uint64_t seed, uint64_t begin,
                           uint64_t count, uint32_t flags, mw::CallMark& mark, Pending& P) {
   const size_t nprog = ps.size();
-  std::vector<const Prog*> progs(nprog);
-  for (size_t i = 0; i < nprog; ++i) progs[i] = ps[i].get();
   mark.step("plan", nprog);
   const double t0 = now_ms();
   HIPCHK(hipSetDevice(c->dev));
   (void)hipGetLastError();  // start from a clean error state: launch errors are read back below
-  int rc = 0;
-  // Programs with a specialised kernel (mg_prog_attach_kernel) get one launch
-  // each; the rest share interpreter launches (grid row per program): one of
-  // the threaded-dispatch asm interpreter for the programs it handles, one of
-  // the compiled interpreter for the others.  d_min holds the asm group, then
-  // the compiled group, then the specialised programs.
-  // Programs with an assembled kernel (mg_prog_attach_asm) get one launch each
-  // on the asm interpreter's records, after the interpreter groups.
-  std::vector<size_t> gasm, gcpp, gasb, special;
-  u64 ops = 0;
-  const bool use_asm = asm_enabled();
-  for (size_t i = 0; i < nprog; ++i) {
-    u32 n1 = 0;
-    if (progs[i]->jit_ready()) special.push_back(i);
-    else if (use_asm && progs[i]->afn && count < (1ull << 40) &&
-             asm_lds_fit(progs[i]->dev.n_spill, progs[i]->dev.npool, &n1))
-      gasb.push_back(i);
-    else (use_asm && progs[i]->asm_ok ? gasm : gcpp).push_back(i);
-    ops += progs[i]->ops_per_eval;
-  }
-  // the asm groups need their pools staged in LDS (programs whose pool does not
-  // fit run on the compiled interpreter); one group per register layout
-  // (kAsmKernel: the wide, narrow and quarter kernels)
-  std::vector<size_t> glay[kAsmLayouts];
-  u32 lay_nlds[kAsmLayouts] = {0, 0, 0};
-  {
-    u32 ms[kAsmLayouts] = {0, 0, 0}, mp[kAsmLayouts] = {0, 0, 0};
-    for (size_t i : gasm) {
-      u32 n1 = 0;
-      const u8 L = progs[i]->asm_layout;
-      if (count < (1ull << 40) && asm_lds_fit(progs[i], &n1)) {
-        glay[L].push_back(i);
-        ms[L] = std::max(ms[L], progs[i]->dev.n_spill);
-        mp[L] = std::max(mp[L], progs[i]->dev.npool);
-      } else {
-        gcpp.push_back(i);
-      }
-    }
-    for (int L = 0; L < kAsmLayouts; ++L)
-      if (!glay[L].empty()) (void)asm_lds_fit(ms[L], mp[L], &lay_nlds[L], (u8)L, true);
-  }
-  std::vector<size_t> interp;
-  for (int L = 0; L < kAsmLayouts; ++L) interp.insert(interp.end(), glay[L].begin(), glay[L].end());
-  const size_t nasm = interp.size();
-  interp.insert(interp.end(), gcpp.begin(), gcpp.end());
-  const size_t ni = interp.size();
-  interp.insert(interp.end(), gasb.begin(), gasb.end());   // d_progs / d_min: then the assembled ones
-  const size_t nia = interp.size();
-  std::vector<ProgDev> hp;
-  for (size_t j = 0; j < nia; ++j)   // the asm groups read the predecoded code
-    hp.push_back(j < nasm ? progs[interp[j]]->adev : progs[interp[j]]->dev);
-  const u64 nchunks = (count + kBlock - 1) / kBlock;
-  struct Group {
-    size_t first, n;
-    u64 gx;
-    u32 nlds, max_pool;
-  } groups[kAsmLayouts + 1];   // the asm layouts' groups, then the compiled interpreter's
-  {
-    size_t first = 0;
-    for (int L = 0; L < kAsmLayouts; ++L) {
-      groups[L] = {first, glay[L].size(), 1, 0, 0};
-      first += glay[L].size();
-    }
-    groups[kAsmLayouts] = {nasm, gcpp.size(), 1, 0, 0};
-  }
-  size_t spill_need = 4;
-  for (int gi = 0; gi <= kAsmLayouts; ++gi) {
-    Group& G = groups[gi];
-    if (!G.n) continue;
-    u32 max_spill = 0;
-    for (size_t j = G.first; j < G.first + G.n; ++j) {
-      max_spill = std::max(max_spill, hp[j].n_spill);
-      G.max_pool = std::max(G.max_pool, hp[j].npool);
-    }
-    // enough blocks to fill the chip several times over, split across programs
-    G.gx = std::max<u64>(1, (u64)c->ncu * 8 / G.n);
-    G.gx = std::min<u64>(G.gx, nchunks);
-    u64 nthreads = G.gx * G.n * kBlock;
-    if (gi < kAsmLayouts) {
-      // the asm groups: one 1D grid, blocks in proportion to each program's
-      // instructions (its cost per candidate), at least one, at most its chunks
-      double wsum = 0;
-      for (size_t j = G.first; j < G.first + G.n; ++j) wsum += std::max<u32>(1, hp[j].n_insn);
-      const double B = (double)std::max<u64>(G.n, (u64)c->ncu * 8);
-      u64 at = 0;
-      for (size_t j = G.first; j < G.first + G.n; ++j) {
-        const u64 b = std::min<u64>(nchunks, std::max<u64>(1, (u64)(B * std::max<u32>(1, hp[j].n_insn) / wsum)));
-        hp[j].first_block = (u32)at;
-        at += b;
-      }
-      G.gx = at;   // the whole grid
-      nthreads = G.gx * kBlock;
-    }
-    G.nlds = gi < kAsmLayouts ? lay_nlds[gi] : std::min(max_spill, kLdsSpillWords);
-    spill_need = std::max(spill_need, (size_t)(max_spill - G.nlds) * nthreads * sizeof(u32));
-  }
-  // assembled kernels: records kAsmLayouts.. (one program, the whole chip each)
-  const u64 agx = std::min<u64>((u64)c->ncu * 8, nchunks);
-  std::vector<AsmArgs> ha(kAsmLayouts + gasb.size());   // the layouts' groups, then the assembled kernels
-  for (size_t k = 0; k < gasb.size(); ++k) {
-    const ProgDev& d = hp[ni + k];
-    AsmArgs& r = ha[kAsmLayouts + k];
-    (void)asm_lds_fit(d.n_spill, d.npool, &r.nlds);
-    r.seed = seed;
-    r.begin = begin;
-    r.end = begin + count;
-    r.flags = flags;
-    r.gstride = (u32)(agx * kBlock * 4);
-    r.nchunks = (u32)nchunks;
-    r.gdx = (u32)agx;
-    r.verdict = nullptr;
-    spill_need = std::max(spill_need, (size_t)(d.n_spill - r.nlds) * agx * kBlock * sizeof(u32));
-  }
-  const bool need_args = nasm || !gasb.empty();
+  std::vector<ProgFacts> facts(nprog);
+  for (size_t i = 0; i < nprog; ++i) facts[i] = facts_of(ps[i].get());
+  SearchPlan S = plan_search(facts.data(), nprog, count, c->ncu, asm_enabled(), wide_lds_words());
+  const size_t nasb = S.assembled.size();
+  // AsmArgs records: the layouts' groups, then the assembled kernels
+  const size_t nargs = S.nasm || nasb ? kAsmLayouts + nasb : 0;
   mark.step("buffers", nprog);
-  rc = ensure_launch(c, nprog, need_args ? ha.size() : 0);
+  int rc = ensure_launch(c, nprog, nargs);
   if (rc) return rc;
-  if (nia) {
-    rc = ensure_spill(c, spill_need);
+  if (S.nia) {
+    rc = ensure_spill(c, S.spill_need);
     if (rc) return rc;
   }
-  for (size_t k = 0; k < gasb.size(); ++k) ha[kAsmLayouts + k].spillbuf = c->d_spill;
-  for (int gi = 0; gi < kAsmLayouts && need_args; ++gi) {
-    AsmArgs& aa = ha[gi];
-    aa.seed = seed;
-    aa.begin = begin;
-    aa.end = begin + count;
-    aa.flags = flags;
-    aa.nlds = groups[gi].nlds;
-    aa.gstride = (u32)(groups[gi].gx * kBlock * 4);   // a 1D grid of gx blocks (above)
-    aa.nchunks = (u32)nchunks;
-    aa.gdx = (u32)groups[gi].gx;
-    aa.nprog = (u32)groups[gi].n;
-    aa.spillbuf = c->d_spill;   // the launches run one after the other on the stream
-    aa.verdict = nullptr;
+  std::vector<ProgDev> hp(S.nia);
+  for (size_t j = 0; j < S.nia; ++j) {   // the asm groups read the predecoded code
+    hp[j] = j < S.nasm ? ps[S.interp[j]]->adev : ps[S.interp[j]]->dev;
+    hp[j].first_block = S.first_block[j];
+  }
+  std::vector<AsmArgs> ha(nargs);   // (the launches run one after the other on the stream: one spill buffer)
+  for (size_t k = 0; k < nargs; ++k) {
+    if (k < kAsmLayouts) {
+      const SearchPlan::Group& G = S.groups[k];
+      ha[k] = asm_args<AsmArgs>(seed, begin, count, flags, G.gx, G.nlds, (u32)G.n, c->d_spill);
+    } else {
+      const SearchPlan::Assembled& A = S.assembled[k - kAsmLayouts];
+      ha[k] = asm_args<AsmArgs>(seed, begin, count, flags, A.gx, A.nlds, 0, c->d_spill);
+    }
   }
   // one upload: zeroed counters, d_min at MG_NONE, the ProgDev and AsmArgs records
   mark.step("enqueue", count);
@@ -1537,61 +1436,39 @@ static int search_enqueue(Ctx* c, const std::vector<std::shared_ptr<Prog>>& ps, 
   // (a queued program upload), the upload, the kernels and the readback
   const bool gpu_steps = mw::step_times_on() && c->ea && c->eb;
   if (gpu_steps) HIPCHK(hipEventRecord(c->ea, c->stream));
-  HIPCHK(stage_upload(c, nprog, hp.data(), nia, ha.data(), need_args ? ha.size() : 0));
+  HIPCHK(stage_upload(c, nprog, hp.data(), S.nia, ha.data(), nargs));
   HIPCHK(hipEventRecord(c->e0, c->stream));
   for (int gi = 0; gi < kAsmLayouts; ++gi) {
-    const Group& G = groups[gi];
+    const SearchPlan::Group& G = S.groups[gi];
     if (!G.n) continue;
-    const size_t lds = (size_t)G.nlds * kBlock * 4 + (size_t)G.max_pool * 4;
-    hipLaunchKernelGGL(kAsmKernel[gi], dim3((u32)G.gx, 1u), dim3(kBlock), lds, c->stream,
-                       c->d_progs + G.first, (const AsmArgs*)c->d_asmargs + gi, c->d_min + G.first, c->d_counter,
-                       G.nlds);
-    HIPCHK(hipGetLastError());
-  }
-  if (groups[kAsmLayouts].n) {
-    const Group& G = groups[kAsmLayouts];
-    // stage the pools in LDS when they fit beside the spill words (80 KiB per
-    // block keeps two blocks per CU)
-    const size_t spill_bytes = (size_t)G.nlds * kBlock * 4, pool_bytes = (size_t)G.max_pool * 4;
-    const ProgDev* dp = c->d_progs + G.first;
-    u64* dm = c->d_min + G.first;
-#ifdef MW_NO_POOL_LDS   // A/B builds only
-    if (false)
-#else
-    if (G.max_pool && spill_bytes + pool_bytes <= (size_t)kLdsSpillWords * kBlock * 4)
-#endif
-      hipLaunchKernelGGL(mw_search_kernel<true>, dim3((u32)G.gx, (u32)G.n), dim3(kBlock), spill_bytes + pool_bytes,
-                         c->stream, dp, seed, begin, count, flags, dm, c->d_counter, c->d_spill, G.nlds);
-    else
-      hipLaunchKernelGGL(mw_search_kernel<false>, dim3((u32)G.gx, (u32)G.n), dim3(kBlock), spill_bytes,
-                         c->stream, dp, seed, begin, count, flags, dm, c->d_counter, c->d_spill, G.nlds);
-    HIPCHK(hipGetLastError());
-  }
-  for (size_t k = 0; k < gasb.size(); ++k) {
-    rc = launch_assembled(c, progs[gasb[k]], (u32)agx, c->d_progs + ni + k, c->d_asmargs + kAsmLayouts + k,
-                          c->d_min + ni + k, ha[kAsmLayouts + k].nlds);
+    rc = launch_asm(c, nullptr, (u8)gi, c->d_progs + G.first, c->d_asmargs + gi, c->d_min + G.first, c->d_counter,
+                    G.gx, G.nlds, G.max_pool);
     if (rc) return rc;
   }
-  for (size_t j = 0; j < special.size(); ++j) {
-    rc = launch_jit(c, progs[special[j]], seed, begin, count, flags, c->d_min + nia + j, nullptr);
+  if (const SearchPlan::Group& G = S.groups[kAsmLayouts]; G.n) {
+    const auto kernel = G.pool_lds ? mw_search_kernel<true> : mw_search_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((u32)G.gx, (u32)G.n), dim3(kBlock), asm_lds_bytes(G.nlds, G.pool_lds ? G.max_pool : 0),
+                       c->stream, (const ProgDev*)c->d_progs + G.first, seed, begin, count, flags, c->d_min + G.first,
+                       c->d_counter, c->d_spill, G.nlds);
+    HIPCHK(hipGetLastError());
+  }
+  for (size_t k = 0; k < nasb; ++k) {
+    rc = launch_asm(c, ps[S.interp[S.ni + k]]->afn, kWide, c->d_progs + S.ni + k, c->d_asmargs + kAsmLayouts + k,
+                    c->d_min + S.ni + k, c->d_counter, S.assembled[k].gx, S.assembled[k].nlds, 0);
+    if (rc) return rc;
+  }
+  for (size_t j = 0; j < S.special.size(); ++j) {
+    rc = launch_jit(c, ps[S.special[j]].get(), seed, begin, count, flags, c->d_min + S.nia + j, nullptr);
     if (rc) return rc;
   }
   HIPCHK(hipEventRecord(c->e1, c->stream));
   HIPCHK(stage_readback(c, nprog));   // counters and d_min, one copy
   if (gpu_steps) HIPCHK(hipEventRecord(c->eb, c->stream));
   P.ps = ps;
-  P.interp = interp;
-  P.special = special;
-  P.nia = nia;
-  P.slot.assign(nprog, 0);
-  for (size_t j = 0; j < nia; ++j) P.slot[interp[j]] = j;
-  for (size_t j = 0; j < special.size(); ++j) P.slot[special[j]] = nia + j;
+  P.plan = std::move(S);
   P.count = count;
   P.seed = seed;
-  P.ops = ops;
   P.flags = flags;
-  P.nlaunches = gasb.size() + special.size();
-  for (const Group& G : groups) P.nlaunches += G.n ? 1 : 0;
   P.t0 = t0;
   P.gpu_steps = gpu_steps;
   return 0;
@@ -1624,17 +1501,16 @@ static int search_complete(Ctx* c, Pending& P, uint64_t* out_min_idx, mg_stats* 
     for (int k = 0; k < kNCounters; ++k) ctr[k] += stripes[sidx * MW_CTR_STRIPE_WORDS + k];
   // specialised launches under MW_FLAG_NO_COUNT counted nothing: every
   // candidate of the range was evaluated (no stop-after-hit)
-  const u64 evals = ctr[0] + ((P.flags & MW_FLAG_NO_COUNT) ? P.count * P.special.size() : 0u);
-  for (size_t j = 0; j < P.nia; ++j) out_min_idx[P.interp[j]] = mins[j];
-  for (size_t j = 0; j < P.special.size(); ++j) out_min_idx[P.special[j]] = mins[P.nia + j];
+  const u64 evals = ctr[0] + ((P.flags & MW_FLAG_NO_COUNT) ? P.count * P.plan.special.size() : 0u);
+  for (size_t i = 0; i < P.ps.size(); ++i) out_min_idx[i] = mins[P.plan.slot[i]];
   if (st) {
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1));
     st->kernel_ms = ms;
     st->wall_ms = now_ms() - P.t0;
     st->evals = evals;  // summed over every program's blocks
-    st->launches = P.nlaunches;
-    st->ops = (double)evals / (double)P.ps.size() * (double)P.ops;
+    st->launches = P.plan.nlaunches;
+    st->ops = (double)evals / (double)P.ps.size() * (double)P.plan.ops;
     st->lane_div_steps = ctr[1];
     st->lane_div_full = ctr[2];
     st->lane_div_short = ctr[3];
@@ -1643,43 +1519,47 @@ static int search_complete(Ctx* c, Pending& P, uint64_t* out_min_idx, mg_stats* 
   return 0;
 }
 
-int mg_search(mg_ctx* h, mg_prog* const* hprogs, size_t nprog, uint64_t seed, uint64_t begin,
-              uint64_t count, uint32_t flags, uint64_t* out_min_idx, mg_stats* st) {
-  if (!h || !hprogs || !out_min_idx || nprog == 0) return fail(MG_E_ARG, "null argument");
+// What mg_search and mg_search_begin share: the argument checks, the flags as
+// the kernels get them, and the call's entry (handles resolved, reference-held
+// and locked for the whole call, mw_handles.h) on a context with no search pending.
+static int search_enter(mw::Registry<Ctx, Prog>& reg, const char* name, mg_ctx* h, mg_prog* const* hprogs, size_t nprog,
+                        uint64_t begin, uint64_t count, uint32_t* flags, mw::CallMark& mark, CallG& call) {
+  if (!h || !hprogs || nprog == 0) return fail(MG_E_ARG, "null argument");
   if (nprog > 65535) return fail(MG_E_ARG, "too many programs per launch");
   if (count == 0 || begin + count < begin) return fail(MG_E_ARG, "bad candidate range");
-  if (flags & MW_FLAG_STOP_AFTER_HIT) flags &= ~MW_FLAG_NO_COUNT;   // blocks may skip: only the counters know
+  if (*flags & MW_FLAG_STOP_AFTER_HIT) *flags &= ~MW_FLAG_NO_COUNT;   // blocks may skip: only the counters know
   std::vector<u64> ids(nprog);
   for (size_t i = 0; i < nprog; ++i) ids[i] = hid(hprogs[i]);
-  mw::CallMark mark("mg_search");
   mark.step("lock", nprog);
-  CallG call;   // resolved, reference-held and locked for the whole call (mw_handles.h)
-  if (const char* why = mw::enter(g_reg, hid(h), ids.data(), nprog, call)) return fail(MG_E_ARG, std::string("mg_search: ") + why);
+  if (const char* why = mw::enter(reg, hid(h), ids.data(), nprog, call))
+    return fail(MG_E_ARG, std::string(name) + ": " + why);
+  if (call.c->pending.active) return fail(MG_E_ARG, std::string(name) + ": a search begun with mg_search_begin is pending");
+  return 0;
+}
+
+int mg_search(mg_ctx* h, mg_prog* const* hprogs, size_t nprog, uint64_t seed, uint64_t begin,
+              uint64_t count, uint32_t flags, uint64_t* out_min_idx, mg_stats* st) {
+  if (!out_min_idx) return fail(MG_E_ARG, "null argument");
+  mw::CallMark mark("mg_search");
+  CallG call;
+  int rc = search_enter(g_reg, "mg_search", h, hprogs, nprog, begin, count, &flags, mark, call);
+  if (rc) return rc;
   Ctx* c = call.c.get();
-  if (c->pending.active) return fail(MG_E_ARG, "mg_search: a search begun with mg_search_begin is pending");
   Pending P;
-  int rc = search_enqueue(c, call.ps, seed, begin, count, flags, mark, P);
+  rc = search_enqueue(c, call.ps, seed, begin, count, flags, mark, P);
   if (rc) return rc;
   return search_complete(c, P, out_min_idx, st, mark);
 }
 
 int mg_search_begin(mg_ctx* h, mg_prog* const* hprogs, size_t nprog, uint64_t seed, uint64_t begin,
                     uint64_t count, uint32_t flags) {
-  if (!h || !hprogs || nprog == 0) return fail(MG_E_ARG, "null argument");
-  if (nprog > 65535) return fail(MG_E_ARG, "too many programs per launch");
-  if (count == 0 || begin + count < begin) return fail(MG_E_ARG, "bad candidate range");
-  if (flags & MW_FLAG_STOP_AFTER_HIT) flags &= ~MW_FLAG_NO_COUNT;
-  std::vector<u64> ids(nprog);
-  for (size_t i = 0; i < nprog; ++i) ids[i] = hid(hprogs[i]);
   mw::CallMark mark("mg_search_begin");
-  mark.step("lock", nprog);
   CallG call;
-  if (const char* why = mw::enter(g_reg, hid(h), ids.data(), nprog, call))
-    return fail(MG_E_ARG, std::string("mg_search_begin: ") + why);
+  int rc = search_enter(g_reg, "mg_search_begin", h, hprogs, nprog, begin, count, &flags, mark, call);
+  if (rc) return rc;
   Ctx* c = call.c.get();
-  if (c->pending.active) return fail(MG_E_ARG, "mg_search_begin: a search begun earlier is pending");
   Pending P;
-  int rc = search_enqueue(c, call.ps, seed, begin, count, flags, mark, P);
+  rc = search_enqueue(c, call.ps, seed, begin, count, flags, mark, P);
   if (rc) {
     hipStreamSynchronize(c->stream);
     return rc;
@@ -1712,8 +1592,7 @@ static int witness_enqueue(Ctx* c, const std::shared_ptr<Ctx>& cref, Pending& P,
     std::shared_ptr<Prog> wp;
     rc = load_locked(cref, wd[i], wp);
     if (rc) return rc;
-    u32 nlds = 0;
-    if (!wp->asm_ok || !asm_enabled() || !asm_lds_fit(wp.get(), &nlds)) {   // the caller evaluates it later
+    if (prog_engine(wp.get(), 1).kind != kAsm) {   // the caller evaluates it later
       release_prog(*wp);
       continue;
     }
@@ -1722,17 +1601,19 @@ static int witness_enqueue(Ctx* c, const std::shared_ptr<Ctx>& cref, Pending& P,
   }
   const size_t nw = W.wps.size();
   if (!nw) return 0;
-  // device block: slots | ProgDev records | AsmArgs records | counter sink |
-  // verdicts | trace rows
+  // device block: slots | ProgDev records | AsmArgs records | sink (the
+  // launches' counter words, zeroed, then their out_min word at MG_NONE: the
+  // search's own counters and d_min stay untouched) | verdicts | trace rows
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  constexpr size_t kSinkMin = 8;   // past the kNCounters counter words
   const size_t o_prog = up(nw * 4), o_args = up(o_prog + nw * sizeof(ProgDev)),
-               o_ctr = up(o_args + nw * sizeof(AsmArgs)), o_verd = up(o_ctr + 8 * sizeof(u64));
+               o_ctr = up(o_args + nw * sizeof(AsmArgs)), o_verd = up(o_ctr + (kSinkMin + 1) * sizeof(u64));
   size_t rows = 0;
   for (auto& wp : W.wps) {
     W.trace_off.push_back(rows);
     rows += wp->desc.n_trace_rows;
   }
-  const size_t o_tr = o_verd + nw * 4, total = o_tr + rows * 4, head = o_ctr;
+  const size_t o_tr = o_verd + nw * 4, total = o_tr + rows * 4, head = o_verd;
   W.verd_off = o_verd;
   W.rb_bytes = total - o_verd;
   if (W.rb_bytes > kReadbackMax || !ensure_readback(c, W.rb_bytes)) {   // too big to read back in one copy
@@ -1740,11 +1621,13 @@ static int witness_enqueue(Ctx* c, const std::shared_ptr<Ctx>& cref, Pending& P,
     W.wps.clear();
     return 0;
   }
+  std::vector<u32> wnlds(nw);   // one block each: its LDS spill rows, the rest in the global buffer
   size_t spill = 4;
-  for (auto& wp : W.wps) {
-    u32 nlds = 0;
-    (void)asm_lds_fit(wp.get(), &nlds);
-    spill = std::max(spill, (size_t)(wp->dev.n_spill - nlds) * kBlock * sizeof(u32));
+  for (size_t k = 0; k < nw; ++k) {
+    const Prog* wp = W.wps[k].get();
+    (void)asm_lds_fit(wp->dev.n_spill, wp->dev.npool, asm_budget_words(wp->asm_layout, false, wide_lds_words()),
+                      &wnlds[k]);
+    spill = std::max(spill, (size_t)(wp->dev.n_spill - wnlds[k]) * kBlock * sizeof(u32));
   }
   int rc = ensure_spill(c, spill);   // (a regrow frees the old buffer: hipFree waits for the search)
   if (rc) return rc;
@@ -1766,24 +1649,16 @@ static int witness_enqueue(Ctx* c, const std::shared_ptr<Ctx>& cref, Pending& P,
   AsmArgs* hargs = (AsmArgs*)(hw + o_args);
   for (size_t k = 0; k < nw; ++k) {
     const Prog* wp = W.wps[k].get();
-    hslot[k] = (u32)P.slot[W.prog_of[k]];
+    hslot[k] = (u32)P.plan.slot[W.prog_of[k]];
     hprog[k] = wp->adev;
     AsmArgs& a = hargs[k];
-    a.seed = 0;   // set below: the search's seed
-    a.begin = 0;
-    a.end = 1;    // patched on the device (mw_witness_index_kernel)
-    a.flags = 0;
-    (void)asm_lds_fit(wp, &a.nlds);
-    a.gstride = kBlock * 4;
-    a.nchunks = 1;
-    a.gdx = 1;
-    a.nprog = 0;
-    a.spillbuf = c->d_spill;
+    // one candidate in one block; begin and end are patched on the device (mw_witness_index_kernel)
+    a = asm_args<AsmArgs>(P.seed, 0, 1, 0, 1, wnlds[k], 0, c->d_spill);
     a.verdict = (u32*)(d + o_verd) + k;
     a.trace = (u32*)(d + o_tr) + W.trace_off[k];
     a.ncand = 1;
   }
-  for (size_t k = 0; k < nw; ++k) hargs[k].seed = P.seed;
+  ((u64*)(hw + o_ctr))[kSinkMin] = MG_NONE;
   mark.step("witness enqueue", nw);
   HIPCHK(hipMemcpyAsync(d, hw, head, hipMemcpyHostToDevice, c->stream));
   for (size_t k = 0; k < nw; ++k)
@@ -1794,12 +1669,9 @@ static int witness_enqueue(Ctx* c, const std::shared_ptr<Ctx>& cref, Pending& P,
   HIPCHK(hipGetLastError());
   for (size_t k = 0; k < nw; ++k) {
     const Prog* wp = W.wps[k].get();
-    const u32 nlds = hargs[k].nlds;
-    const size_t lds = (size_t)nlds * kBlock * 4 + (size_t)wp->dev.npool * 4;
-    hipLaunchKernelGGL(kAsmKernel[wp->asm_layout], dim3(1u, 1u), dim3(kBlock), lds, c->stream,
-                       (const ProgDev*)(d + o_prog) + k, (const AsmArgs*)(d + o_args) + k,
-                       (u64*)(d + o_ctr) + 1, (u64*)(d + o_ctr), nlds);
-    HIPCHK(hipGetLastError());
+    rc = launch_asm(c, nullptr, wp->asm_layout, (const ProgDev*)(d + o_prog) + k, (const AsmArgs*)(d + o_args) + k,
+                    (u64*)(d + o_ctr) + kSinkMin, (u64*)(d + o_ctr), 1, wnlds[k], wp->dev.npool);
+    if (rc) return rc;
   }
   HIPCHK(hipMemcpyAsync(c->h_rb, d + o_verd, W.rb_bytes, hipMemcpyDeviceToHost, c->stream));
   for (size_t k = 0; k < nw; ++k) traced[W.prog_of[k]] = 1;
@@ -1868,23 +1740,9 @@ static int eval_common(Ctx* c, const Prog* p, const uint32_t* leaves_soa, size_t
   if (ntr && !p->trace_full) hipMemsetAsync(d_t, 0, tb, c->stream);
   hipLaunchKernelGGL(mw_eval_kernel, dim3((u32)gx), dim3(kBlock), (size_t)nlds * kBlock * 4, c->stream,
                      p->dev, (const u32*)d_in, (u64)ncand, seed, begin, d_v, d_t, c->d_spill, nlds);
-  hipError_t e = hipGetLastError();
-  const bool pinned = vb + tb <= kReadbackMax && ensure_readback(c, vb + tb);
-  if (e == hipSuccess && pinned) {
-    e = hipMemcpyAsync(c->h_rb, d_v, vb + tb, hipMemcpyDeviceToHost, c->stream);
-  } else {
-    if (e == hipSuccess) e = hipMemcpyAsync(verdict, d_v, vb, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && ntr) e = hipMemcpyAsync(trace, d_t, tb, hipMemcpyDeviceToHost, c->stream);
-  }
-  mw::inflight_step("eval/sync", ncand);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  const hipError_t e = eval_readback(c, hipGetLastError(), "eval/sync", d_v, vb, tb, verdict, trace);
   s_in.synced = s_vt.synced = e == hipSuccess;
   if (e != hipSuccess) return fail(MG_E_HIP, std::string("eval: ") + hipGetErrorString(e));
-  c->uploads_landed();   // the stream drained: a queued program upload has landed
-  if (pinned) {
-    std::memcpy(verdict, c->h_rb, vb);
-    if (ntr) std::memcpy(trace, c->h_rb + vb, tb);
-  }
   return 0;
 }
 
@@ -1912,14 +1770,19 @@ int mg_eval(mg_ctx* h, const mg_prog* hp, const uint32_t* leaves_soa, size_t nca
 // 1 = not applicable (the caller uses mw_eval_kernel).
 static int eval_asm(Ctx* c, const Prog* p, uint64_t seed, uint64_t begin, size_t count, uint32_t* verdict,
                     uint32_t* trace) {
-  if (!asm_enabled() || !p->asm_ok || begin + count < begin || count >= (1ull << 40)) return 1;
+  if (begin + count < begin) return 1;
   const size_t ntr = trace ? (size_t)p->desc.n_trace_rows * count : 0;
   // trace offsets are 32-bit byte offsets in the kernel (asmgen.py store_rows)
   if (trace && (count >= (1ull << 32) || ntr * 4 >= (1ull << 31))) return 1;
-  const bool assembled = p->afn != nullptr && !trace;   // its assembled kernel, else the asm interpreter
+  // its assembled kernel (verdicts only), else the asm interpreter
+  ProgFacts f = facts_of(p);
+  f.jit_ready = false;
+  f.has_assembled = f.has_assembled && !trace;
+  const Engine eng = engine_of(f, asm_enabled(), count, wide_lds_words());
+  if (eng.kind != kAsm && eng.kind != kAssembled) return 1;
+  const bool assembled = eng.kind == kAssembled;
   u32 nlds = 0;
-  if (!(assembled ? asm_lds_fit(p->dev.n_spill, p->dev.npool, &nlds) : asm_lds_fit(p, &nlds))) return 1;
-  const size_t lds = (size_t)nlds * kBlock * 4 + (size_t)p->dev.npool * 4;
+  (void)asm_lds_fit(f.n_spill, f.npool, asm_budget_words(f.asm_layout, assembled, wide_lds_words()), &nlds);
   HIPCHK(hipSetDevice(c->dev));
   (void)hipGetLastError();
   int rc = ensure_launch(c, 1, 1);
@@ -1933,46 +1796,22 @@ static int eval_asm(Ctx* c, const Prog* p, uint64_t seed, uint64_t begin, size_t
   Scratch s_v(c, vb + tb);
   if (!s_v.p) return fail(MG_E_NOMEM, "eval verdict alloc");
   u32 *d_v = s_v.u(), *d_t = ntr ? d_v + count : nullptr;
-  AsmArgs aa{};
-  aa.seed = seed;
-  aa.begin = begin;
-  aa.end = begin + count;
-  aa.flags = 0;
-  aa.nlds = nlds;
-  aa.gstride = (u32)(gx * kBlock * 4);
-  aa.nchunks = (u32)nchunks;
-  aa.gdx = (u32)gx;
-  aa.spillbuf = c->d_spill;
+  AsmArgs aa = asm_args<AsmArgs>(seed, begin, count, 0, gx, nlds, 0, c->d_spill);
   aa.verdict = d_v;
   aa.trace = d_t;
   aa.ncand = (u32)count;
   hipError_t e = ntr && !p->trace_full ? hipMemsetAsync(d_t, 0, tb, c->stream) : hipSuccess;
   if (e == hipSuccess) e = stage_upload(c, 1, assembled ? &p->dev : &p->adev, 1, &aa, 1);
-  if (e == hipSuccess && assembled) {
-    if (launch_assembled(c, p, (u32)gx, c->d_progs, c->d_asmargs, c->d_min, nlds)) return MG_E_HIP;
-  } else if (e == hipSuccess) {
-    hipLaunchKernelGGL(kAsmKernel[p->asm_layout], dim3((u32)gx, 1u), dim3(kBlock), lds, c->stream, c->d_progs,
-                       (const AsmArgs*)c->d_asmargs, c->d_min, c->d_counter, nlds);
-    e = hipGetLastError();
+  if (e == hipSuccess) {
+    rc = launch_asm(c, assembled ? p->afn : nullptr, p->asm_layout, c->d_progs, c->d_asmargs, c->d_min, c->d_counter,
+                    gx, nlds, p->dev.npool);
+    if (rc) return rc;
   }
-  const bool pinned = vb + tb <= kReadbackMax && ensure_readback(c, vb + tb);
-  if (e == hipSuccess && pinned) {
-    e = hipMemcpyAsync(c->h_rb, d_v, vb + tb, hipMemcpyDeviceToHost, c->stream);
-  } else {
-    if (e == hipSuccess) e = hipMemcpyAsync(verdict, d_v, vb, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && ntr) e = hipMemcpyAsync(trace, d_t, tb, hipMemcpyDeviceToHost, c->stream);
-  }
-  mw::inflight_step("eval_asm/sync", count);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  e = eval_readback(c, e, "eval_asm/sync", d_v, vb, tb, verdict, trace);
   s_v.synced = e == hipSuccess;
   if (e != hipSuccess)
     return fail(MG_E_HIP, std::string(assembled ? "eval (assembled kernel): " : "eval (asm interpreter): ") +
                               hipGetErrorString(e));
-  c->uploads_landed();   // the stream drained: a queued program upload has landed
-  if (pinned) {
-    std::memcpy(verdict, c->h_rb, vb);
-    if (ntr) std::memcpy(trace, c->h_rb + vb, tb);
-  }
   return 0;
 }
 

@@ -1,0 +1,217 @@
+// mw_launch_plan.h — what a search launches, decided before anything is
+// enqueued: each program's engine, the record order, the grids, the LDS split
+// between spill words and pool, the global spill size and the launch count.
+// Host-only C++ with no HIP header; shared by the product library
+// (mw_kernels.hip, which turns a SearchPlan into records and launches) and the
+// CPU test that checks the arithmetic (tests/native/plan_check.cpp).
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+namespace mw {
+
+typedef uint8_t u8;
+typedef uint32_t u32;
+typedef uint64_t u64;
+
+constexpr int kBlock = 256;
+// Spill area: n_spill words per lane (a W spill slot is 8 consecutive words, an
+// N slot one; the compiler puts the most-used words first).  Words
+// [0, kLdsSpillWords) live in LDS as [word][lane] (consecutive lanes ->
+// consecutive banks): 80 words = 80 KiB per 256-lane block, so two blocks (8
+// waves) still fit a CU's 160 KiB; the rest in the global spill buffer,
+// [word][thread].
+constexpr u32 kLdsSpillWords = 80;
+
+// the asm interpreter's kernels by register layout (Prog::asm_layout)
+enum AsmLayout : u8 { kWide = 0, kNarrow = 1, kQuarter = 2, kAsmLayouts = 3 };
+// The narrow-layout kernel's budget: 52 KiB per block, so three blocks (three
+// waves per SIMD) fit a CU's 160 KiB; the quarter layout's 40 KiB (four).
+constexpr u32 kLdsSpillWordsByLayout[kAsmLayouts] = {kLdsSpillWords, 52, 40};
+
+// The LDS budget of an asm launch in spill-word rows (1 KiB each).  An
+// assembled kernel's LDS is a fixed 80 KiB array (mw_asmjit_shell.hip); the
+// interpreter's kernels get their layout's budget, the wide one wide_words
+// (kLdsSpillWords unless MYTHRIL_AMD_ASM_WIDE_LDS overrides it).
+inline u32 asm_budget_words(u8 layout, bool assembled, u32 wide_words) {
+  if (assembled) return kLdsSpillWords;
+  return layout == kWide ? wide_words : kLdsSpillWordsByLayout[layout];
+}
+
+// LDS words of spill area for an asm launch whose largest pool has max_pool
+// words, within a budget of `words` rows: the pool is staged whole in LDS, the
+// hottest spill words take what is left and the rest spill to the global
+// buffer.  False if the pool alone does not fit (the programs then run on the
+// compiled interpreter).
+inline bool asm_lds_fit(u32 max_spill, u32 max_pool, u32 words, u32* nlds) {
+  const size_t budget = (size_t)words * kBlock * 4, pool_bytes = (size_t)max_pool * 4;
+  if (pool_bytes > budget) return false;
+  const u32 pool_words_lds = (u32)((pool_bytes + kBlock * 4 - 1) / (kBlock * 4));  // in spill-word rows
+  *nlds = std::min(max_spill, words - pool_words_lds);
+  return true;
+}
+
+// dynamic LDS of an asm launch: nlds spill rows, then the pool
+inline size_t asm_lds_bytes(u32 nlds, u32 npool) { return (size_t)nlds * kBlock * 4 + (size_t)npool * 4; }
+
+// An asm launch record (mw_asm_abi.h AsmArgs; a template so that this header
+// needs no HIP): gx blocks stride the chunks of [begin, begin + count).  The
+// caller adds verdict, trace and ncand for an evaluation.
+template <class Args>
+inline Args asm_args(u64 seed, u64 begin, u64 count, u32 flags, u64 gx, u32 nlds, u32 nprog, u32* spillbuf) {
+  Args a{};
+  a.seed = seed;
+  a.begin = begin;
+  a.end = begin + count;
+  a.flags = flags;
+  a.nlds = nlds;
+  a.gstride = (u32)(gx * kBlock * 4);   // bytes between a spill word's rows: one u32 per thread of the grid
+  a.nchunks = (u32)((count + kBlock - 1) / kBlock);
+  a.gdx = (u32)gx;
+  a.nprog = nprog;
+  a.spillbuf = spillbuf;
+  return a;
+}
+
+// What the plan needs to know of a loaded program.
+struct ProgFacts {
+  u32 n_spill = 0, npool = 0, n_insn = 0;
+  u64 ops_per_eval = 0;
+  bool asm_ok = false;         // every opcode and leaf kind has an asm handler
+  u8 asm_layout = kWide;       // the layout it is predecoded for
+  bool has_assembled = false;  // mg_prog_attach_asm
+  bool jit_ready = false;      // mg_prog_attach_kernel, every part
+};
+
+// The kernel that searches a program; the values are mg_prog_engine's codes.
+enum EngineKind : u8 { kCompiled = 0, kAsm = 1, kSpecialised = 2, kAssembled = 3 };
+struct Engine { EngineKind kind; u8 layout; };   // layout: the interpreter kernel of a kAsm program
+
+// The engine rule.  A specialised kernel wins; then an assembled one; then the
+// asm interpreter, for programs it handles whose pool fits its LDS budget; the
+// compiled interpreter runs the rest.  The asm engines count chunks in 32
+// bits: ranges from 2^40 candidates stay on the compiled interpreter.
+inline Engine engine_of(const ProgFacts& f, bool use_asm, u64 count, u32 wide_words) {
+  u32 nlds = 0;
+  if (f.jit_ready) return {kSpecialised, kWide};
+  if (use_asm && count < (1ull << 40)) {
+    if (f.has_assembled && asm_lds_fit(f.n_spill, f.npool, asm_budget_words(kWide, true, wide_words), &nlds))
+      return {kAssembled, kWide};
+    if (f.asm_ok && asm_lds_fit(f.n_spill, f.npool, asm_budget_words(f.asm_layout, false, wide_words), &nlds))
+      return {kAsm, f.asm_layout};
+  }
+  return {kCompiled, kWide};
+}
+
+struct SearchPlan {
+  // Record order (d_progs and d_min): the asm interpreter's groups by layout
+  // [0, nasm), the compiled interpreter's group [nasm, ni), the assembled
+  // kernels' programs [ni, nia); the specialised programs' d_min words follow.
+  std::vector<size_t> interp, special;   // program indices in that order
+  std::vector<size_t> slot;              // program i's word in d_min
+  size_t nasm = 0, ni = 0, nia = 0;
+  struct Group {
+    size_t first = 0, n = 0;   // its records
+    u64 gx = 1;                // asm: the whole 1-D grid; compiled: grid x (grid y: the program)
+    u32 nlds = 0, max_pool = 0;
+    bool pool_lds = false;     // compiled group: the pools are staged in LDS
+  } groups[kAsmLayouts + 1];   // the asm layouts' groups, then the compiled interpreter's
+  std::vector<u32> first_block;   // per record: its first block in its asm group's grid (else 0)
+  struct Assembled { u64 gx; u32 nlds; };
+  std::vector<Assembled> assembled;   // records [ni, nia): one launch each
+  size_t spill_need = 4;              // bytes of global spill buffer
+  size_t nlaunches = 0;
+  u64 ops = 0;                        // sum of ops_per_eval
+};
+
+// Programs with a specialised kernel get one launch each; the rest share
+// interpreter launches: one of the asm interpreter per register layout for
+// the programs it handles (a 1-D grid split between them), one of the
+// compiled interpreter for the others (grid row per program).  Programs with
+// an assembled kernel get one launch each, after the interpreter groups.
+inline SearchPlan plan_search(const ProgFacts* facts, size_t n, u64 count, int ncu, bool use_asm, u32 wide_words) {
+  SearchPlan S;
+  // (late: programs the asm interpreter handles but this launch cannot give
+  // it, a pool too big for LDS or a range too long; after the compiled group's others)
+  std::vector<size_t> glay[kAsmLayouts], gcpp, late, gasb;
+  for (size_t i = 0; i < n; ++i) {
+    const Engine e = engine_of(facts[i], use_asm, count, wide_words);
+    if (e.kind == kSpecialised) S.special.push_back(i);
+    else if (e.kind == kAssembled) gasb.push_back(i);
+    else if (e.kind == kAsm) glay[e.layout].push_back(i);
+    else (use_asm && facts[i].asm_ok ? late : gcpp).push_back(i);
+    S.ops += facts[i].ops_per_eval;
+  }
+  for (int L = 0; L < kAsmLayouts; ++L) {
+    S.groups[L].first = S.interp.size();
+    S.groups[L].n = glay[L].size();
+    S.interp.insert(S.interp.end(), glay[L].begin(), glay[L].end());
+  }
+  S.nasm = S.interp.size();
+  gcpp.insert(gcpp.end(), late.begin(), late.end());
+  S.groups[kAsmLayouts].first = S.nasm;
+  S.groups[kAsmLayouts].n = gcpp.size();
+  S.interp.insert(S.interp.end(), gcpp.begin(), gcpp.end());
+  S.ni = S.interp.size();
+  S.interp.insert(S.interp.end(), gasb.begin(), gasb.end());
+  S.nia = S.interp.size();
+  S.slot.assign(n, 0);
+  for (size_t j = 0; j < S.nia; ++j) S.slot[S.interp[j]] = j;
+  for (size_t j = 0; j < S.special.size(); ++j) S.slot[S.special[j]] = S.nia + j;
+  S.first_block.assign(S.nia, 0);
+
+  const u64 nchunks = (count + kBlock - 1) / kBlock;
+  for (int gi = 0; gi <= kAsmLayouts; ++gi) {
+    SearchPlan::Group& G = S.groups[gi];
+    if (!G.n) continue;
+    u32 max_spill = 0;
+    for (size_t j = G.first; j < G.first + G.n; ++j) {
+      max_spill = std::max(max_spill, facts[S.interp[j]].n_spill);
+      G.max_pool = std::max(G.max_pool, facts[S.interp[j]].npool);
+    }
+    // enough blocks to fill the chip several times over, split across programs
+    G.gx = std::max<u64>(1, (u64)ncu * 8 / G.n);
+    G.gx = std::min<u64>(G.gx, nchunks);
+    u64 nthreads = G.gx * G.n * kBlock;
+    if (gi < kAsmLayouts) {
+      // the asm groups: one 1D grid, blocks in proportion to each program's
+      // instructions (its cost per candidate), at least one, at most its chunks
+      double wsum = 0;
+      for (size_t j = G.first; j < G.first + G.n; ++j) wsum += std::max<u32>(1, facts[S.interp[j]].n_insn);
+      const double B = (double)std::max<u64>(G.n, (u64)ncu * 8);
+      u64 at = 0;
+      for (size_t j = G.first; j < G.first + G.n; ++j) {
+        const u64 b = std::min<u64>(
+            nchunks, std::max<u64>(1, (u64)(B * std::max<u32>(1, facts[S.interp[j]].n_insn) / wsum)));
+        S.first_block[j] = (u32)at;
+        at += b;
+      }
+      G.gx = at;   // the whole grid
+      nthreads = G.gx * kBlock;
+      (void)asm_lds_fit(max_spill, G.max_pool, asm_budget_words((u8)gi, false, wide_words), &G.nlds);
+    } else {
+      G.nlds = std::min(max_spill, kLdsSpillWords);
+      // stage the pools in LDS when they fit beside the spill words (80 KiB per
+      // block keeps two blocks per CU)
+#ifndef MW_NO_POOL_LDS   // defined in A/B builds only
+      G.pool_lds = G.max_pool && asm_lds_bytes(G.nlds, G.max_pool) <= (size_t)kLdsSpillWords * kBlock * 4;
+#endif
+    }
+    S.spill_need = std::max(S.spill_need, (size_t)(max_spill - G.nlds) * nthreads * sizeof(u32));
+    ++S.nlaunches;
+  }
+  // assembled kernels: one program, the whole chip each
+  const u64 agx = std::min<u64>((u64)ncu * 8, nchunks);
+  for (size_t i : gasb) {
+    u32 nlds = 0;
+    (void)asm_lds_fit(facts[i].n_spill, facts[i].npool, asm_budget_words(kWide, true, wide_words), &nlds);
+    S.assembled.push_back({agx, nlds});
+    S.spill_need = std::max(S.spill_need, (size_t)(facts[i].n_spill - nlds) * agx * kBlock * sizeof(u32));
+  }
+  S.nlaunches += gasb.size() + S.special.size();
+  return S;
+}
+
+}  // namespace mw

@@ -39,7 +39,7 @@ NP = 256                       # operand tuples per case (pool entries, 8 index 
 WIDE = (33, 64, 160, 255, 256)
 NARROW = (1, 8, 31, 32)
 WIDTHS = NARROW + WIDE
-# the asm interpreter's quarter layout stages the whole pool in LDS (mw_kernels.hip asm_lds_fit)
+# the asm interpreter's quarter layout stages the whole pool in LDS (mw_launch_plan.h asm_lds_fit)
 POOL_WORDS_MAX = isa.ASM_LDS_WORDS["quarter"] * 256
 MAX_CONJUNCTS = 4
 

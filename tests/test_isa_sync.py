@@ -6,13 +6,13 @@ checked against mw_isa.h by tests/test_build.py)."""
 
 def test_layout_limits_match_the_library():
     """isa.ASM_LDS_WORDS / ASM_NK_BY_LAYOUT (engine._lands_on) mirror
-    mw_kernels.hip kLdsSpillWordsByLayout and the generated MW_ASM_NK_* (ADVICE r5)."""
+    mw_launch_plan.h kLdsSpillWordsByLayout and the generated MW_ASM_NK_* (ADVICE r5)."""
     import re
     from pathlib import Path
 
     from mythril_amd import isa
     csrc = Path(__file__).resolve().parent.parent / "mythril_amd" / "csrc"
-    k = (csrc / "mw_kernels.hip").read_text()
+    k = (csrc / "mw_launch_plan.h").read_text()
     m = re.search(r"kLdsSpillWordsByLayout\[kAsmLayouts\] = \{kLdsSpillWords, (\d+), (\d+)\}", k)
     assert m and int(m.group(1)) == isa.ASM_LDS_WORDS["narrow"] and int(m.group(2)) == isa.ASM_LDS_WORDS["quarter"]
     assert f"constexpr u32 kLdsSpillWords = {isa.ASM_LDS_WORDS['wide']};" in k
