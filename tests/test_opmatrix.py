@@ -1,8 +1,9 @@
 """The opcode x width matrix (tests/opmatrix.py) on the CPU: every case gives
 its expected verdicts on the host emulator (the interpreter's own sources
 built for x86) and on oracle/c (the reference alone, no kernel source), and
-the matrix covers every opcode of the ISA and of the asm engines apart from
-the exclusions written here.  tests/test_gpu_opmatrix.py runs the same cases
+the matrix, with the leaf matrix's calldata words (tests/leafmatrix.py),
+covers every opcode of the ISA and of the asm engines apart from the
+exclusions written here.  tests/test_gpu_opmatrix.py runs the same cases
 on every device engine.
 """
 import numpy as np
@@ -10,7 +11,7 @@ import pytest
 
 from mythril_amd import hostemu, isa
 from oracle import cdag
-from tests import opmatrix
+from tests import leafmatrix, opmatrix
 
 SEED = 1
 # the launch shapes of the GPU test: one chunk, and a ragged range past 2^32
@@ -33,8 +34,10 @@ NOT_IN_MATRIX = {
     "CHECK_IMPEQW": "as CHECK_IMP",
     "CHECK_IMPEQK": "a keyed congruence premise (test_congruence, test_gpu_asm.test_asm_corpus_verdicts)",
     "CHECK_GRID": "a congruence grid row (test_grid, test_gpu_asm.test_asm_corpus_verdicts)",
-    "W_CDINS": "a guarded calldata byte chain (test_lower_names, test_gpu_asm.test_asm_corpus_verdicts)",
 }
+# ... and the opcodes whose cases are the leaf matrix's (tests/leafmatrix.py): W_CDINS draws its
+# calldata byte itself, so its value-level cases vary the generator (the "calldata" class there)
+IN_LEAF_MATRIX = {"W_CDINS"}
 # ... and the asm engines' opcodes no asm-eligible case holds: the same, and nothing else
 NOT_IN_ASM_MATRIX = {k: v for k, v in NOT_IN_MATRIX.items() if k in isa.ASM_OPCODES}
 
@@ -94,11 +97,16 @@ def test_declared_asm_eligibility(cases):
 
 def test_opcode_coverage(cases):
     """A new opcode without a matrix case fails here."""
-    seen = set().union(*[c.opcodes() for c in cases])
+    own = set().union(*[c.opcodes() for c in cases])
+    assert IN_LEAF_MATRIX.isdisjoint(own) and IN_LEAF_MATRIX.isdisjoint(NOT_IN_MATRIX)
+    # the leaf matrix adds the opcodes named above and nothing else: any other opcode needs a case here
+    leaf = [c for c in leafmatrix.cases() if c.expect]
+    seen = own | (set().union(*[c.opcodes() for c in leaf]) & IN_LEAF_MATRIX)
     missing = set(isa.OPCODES) - seen
     assert missing == set(NOT_IN_MATRIX), (sorted(missing - set(NOT_IN_MATRIX)), sorted(set(NOT_IN_MATRIX) - missing))
     # the asm engines: what their eligible cases hold
-    seen_asm = set().union(*[c.opcodes() for c in cases if c.asm])
+    seen_asm = set().union(*[c.opcodes() for c in cases if c.asm]) | \
+        (set().union(*[c.opcodes() for c in leaf if c.asm]) & IN_LEAF_MATRIX)
     missing = set(isa.ASM_OPCODES) - seen_asm
     assert missing == set(NOT_IN_ASM_MATRIX), (sorted(missing - set(NOT_IN_ASM_MATRIX)),
                                                sorted(set(NOT_IN_ASM_MATRIX) - missing))

@@ -53,9 +53,16 @@ def main():
         print("tests/test_gpu_opmatrix.py module ranges=%s:" % ranges,
               jit.compile_device(jit_programs(), variants="x", ranges=ranges)[2], "s", flush=True)
 
+    def leafmatrix(lds_leaves):
+        from tests.leafmatrix import jit_programs
+        print("tests/test_gpu_leafmatrix.py module lds_leaves=%d:" % lds_leaves,
+              jit.compile_device(jit_programs(), variants="x", lds_leaves=lds_leaves)[2], "s", flush=True)
+
     from config_bench import warm_jobs as config_jobs   # tools/config_bench.py (C2-C4 solver-log queries)
     jobs += config_jobs() + [gpu_jit_modules, constant_divisors, mul_cols]
     jobs += [lambda: opmatrix(True), lambda: opmatrix(False)]
+    from tests.leafmatrix import JIT_LDS_LEAVES
+    jobs += [lambda: leafmatrix(0), lambda: leafmatrix(JIT_LDS_LEAVES)]
     if jit.RANGES:   # otherwise after the pool: that module is built with the switch on
         jobs.append(ranges)
     if "--opbench" in sys.argv:
