@@ -9,6 +9,9 @@
  *   mg_search     replaces z3 Optimize.check() for feasibility-only queries
  *                 (mythril/laser/smt/solver/solver.py:50-66, reached from
  *                  mythril/support/model.py:58 get_model)
+ *   mg_search_min replaces z3 Optimize.minimize() + check() for a bound on the
+ *                 first objective (mythril/laser/smt/solver/solver.py:109-114,
+ *                  reached from mythril/analysis/solver.py:216-256)
  *   mg_eval       replaces z3 ModelRef.eval / substitute+simplify for a batch
  *                 of assignments (mythril/laser/smt/model.py:52-59)
  *   mg_keccak256  replaces _pysha3.keccak_256 (mythril/support/support_utils.py:50-59,
@@ -122,6 +125,25 @@ int mg_search_begin(mg_ctx* ctx, mg_prog* const* progs, size_t nprog, uint64_t s
                     uint64_t count, uint32_t flags);
 int mg_search_end(mg_ctx* ctx, uint64_t* out_min_idx, mg_stats* stats, const mg_prog_desc* const* witness,
                   uint32_t* const* out_trace, int32_t* traced);
+
+typedef struct { uint64_t index; uint32_t value[8]; } mg_min_result;
+/* Lowest objective among the witnesses of candidates [begin, begin+count): the
+ * program's trace rows 0..n_trace_rows-1 (1..8 rows) are the objective's limbs,
+ * least significant first (limbs never stored are 0), compared as one unsigned
+ * value of up to 256 bits; equal objectives: the lowest index.  Every candidate
+ * of the range is evaluated, in one launch and one synchronisation.
+ * out->index = MG_NONE (and value = 0) when no candidate satisfies.
+ * It always runs the compiled interpreter (mw_search_min_kernel), whatever
+ * mg_prog_engine says for the program: the asm interpreter, the assembled and
+ * the specialised kernels have no such mode.  Refused with MG_E_ARG for a
+ * program of 0 or more than 8 trace rows, for count == 0, and while a search
+ * begun with mg_search_begin is pending on the context.  Same handle, lock
+ * and in-flight protocol as mg_search.  Replaces Optimize.minimize + check
+ * for the first objective (mythril/laser/smt/solver/solver.py:109-114 and
+ * :51-66, reached from mythril/analysis/solver.py:216-256): a bound from one
+ * pass over the candidates, not the optimum over all assignments. */
+int mg_search_min(mg_ctx* ctx, mg_prog* prog, uint64_t seed, uint64_t begin,
+                  uint64_t count, mg_min_result* out, mg_stats* stats);
 
 /* Evaluate one program on explicit assignments: leaves_soa has n_input_rows
  * rows of ncand u32 (row r, candidate i at [r*ncand + i]).  verdict[i] = 0/1;

@@ -14,6 +14,7 @@
 #include "mw_interp.h"
 #include "mw_keccak.h"
 #include "mw_leaf.h"
+#include "mw_min.h"
 
 using namespace mw;
 
@@ -51,11 +52,18 @@ struct HostEnv {
   }
   bool none(bool alive) { return !alive; }
 };
+
+// mwh_search_min: the trace rows 0..7 captured as the candidate's objective
+struct MinHostEnv : HostEnv {
+  u32 obj[kMinLimbs];
+  void store(u32 row, const u32* v, int n) { min_capture(obj, row, v, n); }
+};
 }  // namespace
 
 extern "C" {
 
 int mg_validate_desc(const mg_prog_desc* d);
+int mw_fail(int code, const char* msg);
 
 // Evaluate candidates [0, ncand) (explicit SoA inputs) or generated candidates
 // [begin, begin+ncand) when leaves_soa == NULL.
@@ -126,6 +134,36 @@ long long mwh_count_omp(const mg_prog_desc* d, uint64_t seed, uint64_t begin, si
 }
 
 int mwh_max_threads(void) { return omp_get_max_threads(); }
+
+// The host twin of mg_search_min: generated candidates [begin, begin+ncand)
+// one after the other on the same mw_run, the program's trace rows 0..7
+// captured as the objective (mw_min.h), the same order.
+int mwh_search_min(const mg_prog_desc* d, uint64_t seed, uint64_t begin, uint64_t ncand, mg_min_result* out) {
+  if (!d || !out) return mw_fail(MG_E_ARG, "null argument");
+  int rc = mg_validate_desc(d);
+  if (rc) return rc;
+  if (ncand == 0 || begin + ncand < begin) return mw_fail(MG_E_ARG, "bad candidate range");
+  if (d->n_trace_rows == 0 || d->n_trace_rows > (u32)kMinLimbs)
+    return mw_fail(MG_E_ARG, "mwh_search_min: the objective is the program's trace rows: 1 to 8 of them");
+  std::vector<u32> consts(d->nconst_words + MW_KPAD, 0u);
+  if (d->nconst_words) std::memcpy(consts.data(), d->consts, d->nconst_words * 4);
+  std::vector<u32> code(d->ncode_words + 32, 0u);
+  std::memcpy(code.data(), d->code, d->ncode_words * 4);
+  std::vector<u32> spill;
+  u32 best[kMinLimbs];
+  u64 best_index;
+  min_none(best, best_index);
+  for (u64 i = 0; i < ncand; ++i) {
+    MinHostEnv env{{d->leaves, d->pool, nullptr, nullptr, ncand, i, seed, begin + i, &spill}, {0, 0, 0, 0, 0, 0, 0, 0}};
+    if (mw_run(code.data(), consts.data(), env, true, 0u) && min_less(env.obj, begin + i, best, best_index)) {
+      std::memcpy(best, env.obj, sizeof best);
+      best_index = begin + i;
+    }
+  }
+  out->index = best_index;
+  for (int k = 0; k < kMinLimbs; ++k) out->value[k] = best_index == kMinNone ? 0u : best[k];
+  return 0;
+}
 
 // Leaf values of candidate `cand` (the host twin of mg_witness_leaves).
 int mwh_leaf_values(const mg_prog_desc* d, uint64_t seed, uint64_t cand, uint32_t* out) {

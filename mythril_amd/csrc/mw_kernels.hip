@@ -6,6 +6,10 @@
 //                     lane -> atomicMin(u64) on the program's witness index.
 //   mw_eval_kernel    same interpreter on explicit (SoA) or generated assignments,
 //                     writing per-candidate verdicts and traced node values.
+//   mw_search_min_kernel  mw_search_kernel's loop with the witness of the lowest
+//                     objective (trace rows 0..7) instead of the lowest index:
+//                     a wave and block reduction over 256-bit keys, one record
+//                     per block, reduced by mw_min_reduce_kernel (mg_search_min).
 //   mw_keccak_kernel  one message per lane, Keccak-256.
 // Host side: context (device, stream, events, spill/min/counter buffers),
 // program upload with full validation, thread-local error strings.
@@ -32,6 +36,7 @@
 #include "mw_keccak.h"
 #include "mw_launch_plan.h"
 #include "mw_leaf.h"
+#include "mw_min.h"
 
 extern "C" int mw_fail(int code, const char* msg);
 extern "C" int mg_validate_desc(const mg_prog_desc* d);
@@ -50,6 +55,9 @@ constexpr int kNCounters = 5;  // counter words: evals, then DivCount fields x l
 constexpr size_t kCounterWords = (size_t)(1 + MW_CTR_STRIPES) * MW_CTR_STRIPE_WORDS;
 // the spill area's LDS part (mw_launch_plan.h kLdsSpillWords), then a staged pool
 extern __shared__ u32 lds_spill[];
+
+static_assert(sizeof(MinRecord) == kMinRecordBytes && sizeof(mg_min_result) == sizeof(MinRecord),
+              "mw_launch_plan.h sizes the record buffer; mg_min_result is a record");
 
 typedef const __attribute__((address_space(3))) u32* lptr;
 
@@ -243,6 +251,149 @@ __global__ __launch_bounds__(kBlock, 2) void mw_search_kernel(const ProgDev* __r
     if (lshort) atomicAdd((unsigned long long*)(counter + 3), (unsigned long long)lshort);
     if (lgen) atomicAdd((unsigned long long*)(counter + 4), (unsigned long long)lgen);
   }
+}
+
+namespace {
+
+// mg_search_min's Env: SearchEnv, with the program's trace rows 0..7 captured
+// into the lane's objective (mw_min.h) instead of written anywhere.
+template <bool POOL_LDS>
+struct MinEnv : SearchEnv<POOL_LDS> {
+  u32 obj[kMinLimbs];
+  __device__ void store(u32 row, const u32* v, int n) { min_capture(obj, row, v, n); }
+};
+
+// The lowest (objective, index) key of the block (mw_min.h min_less), in
+// thread 0's obj and index: a butterfly over each wave's 64 lanes with
+// cross-lane moves, then the four waves' keys through `lds` (kMinReduceBytes).
+// Every thread of the block calls it; no thread still uses `lds` for anything else.
+__device__ __forceinline__ void min_block_reduce(u32 obj[kMinLimbs], u64& index, u32* lds) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+    u32 o[kMinLimbs];
+#pragma unroll
+    for (int k = 0; k < kMinLimbs; ++k) o[k] = __shfl_xor(obj[k], m);
+    const u32 lo = __shfl_xor((u32)index, m), hi = __shfl_xor((u32)(index >> 32), m);
+    const u64 oi = ((u64)hi << 32) | lo;
+    if (min_less(o, oi, obj, index)) {
+#pragma unroll
+      for (int k = 0; k < kMinLimbs; ++k) obj[k] = o[k];
+      index = oi;
+    }
+  }
+  constexpr int kWords = kMinLimbs + 2, kWaves = kBlock / 64;
+  __syncthreads();   // the block's last use of lds as spill rows or pool is over
+  if ((threadIdx.x & 63u) == 0u) {
+    u32* r = lds + (threadIdx.x >> 6) * kWords;
+#pragma unroll
+    for (int k = 0; k < kMinLimbs; ++k) r[k] = obj[k];
+    r[kMinLimbs] = (u32)index;
+    r[kMinLimbs + 1] = (u32)(index >> 32);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kWaves; ++w) {
+      const u32* r = lds + w * kWords;
+      u32 o[kMinLimbs];
+#pragma unroll
+      for (int k = 0; k < kMinLimbs; ++k) o[k] = r[k];
+      const u64 oi = ((u64)r[kMinLimbs + 1] << 32) | r[kMinLimbs];
+      if (min_less(o, oi, obj, index)) {
+#pragma unroll
+        for (int k = 0; k < kMinLimbs; ++k) obj[k] = o[k];
+        index = oi;
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ void min_write(MinRecord* out, const u32 obj[kMinLimbs], u64 index) {
+  const bool none = index == kMinNone;   // a block without a witness reports no objective
+  out->index = index;
+#pragma unroll
+  for (int k = 0; k < kMinLimbs; ++k) out->obj[k] = none ? 0u : obj[k];
+}
+
+}  // namespace
+
+// mg_search_min: mw_search_kernel's grid-stride chunk loop over one program,
+// evaluated exhaustively (no early-exit poll), where the witness kept is not
+// the lowest index but the lowest objective: the program's trace rows 0..7 as
+// an unsigned 256-bit value, ties to the lowest index.  Each lane keeps its
+// best (objective, index) over its chunks in registers; the block reduces
+// once, after its loop, and writes one record with plain stores (a 288-bit key
+// has no atomic); mw_min_reduce_kernel reduces the records.  A lane whose
+// verdict is 0, the ragged tail included, never competes, whatever it captured.
+template <bool POOL_LDS>
+__global__ __launch_bounds__(kBlock, 2) void mw_search_min_kernel(const ProgDev* __restrict__ progs, u64 seed,
+                                                               u64 begin, u64 count,
+                                                               MinRecord* __restrict__ records,
+                                                               u64* __restrict__ counter,
+                                                               u32* __restrict__ spillbuf, u32 nlds) {
+  const ProgDev P = progs[0];
+  if (POOL_LDS) {
+    u32* dst = lds_spill + nlds * kBlock;
+    for (u32 i = threadIdx.x; i < P.npool; i += kBlock) dst[i] = P.pool[i];
+    __syncthreads();
+  }
+  const u64 nchunks = (count + kBlock - 1) / kBlock;
+  const u64 end = begin + count;
+  const u64 nthreads = (u64)gridDim.x * kBlock;
+  const u64 gtid = (u64)blockIdx.x * kBlock + threadIdx.x;
+  const u32 lane = threadIdx.x & 63u;
+  u64 evals = 0, lsteps = 0, lfull = 0, lshort = 0, lgen = 0;   // division paths x lanes
+  u32 best[kMinLimbs];
+  u64 best_index;
+  min_none(best, best_index);
+  for (u64 ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+    const u64 cand = begin + ch * kBlock + threadIdx.x;
+    const bool valid = cand < end;
+    MinEnv<POOL_LDS> env{{P.leaves, P.pool, seed, cand, spillbuf, nthreads, gtid, nlds}, {0, 0, 0, 0, 0, 0, 0, 0}};
+    const bool ok = mw_run(P.code, P.consts, env, valid, 0u);
+    if (ok && min_less(env.obj, cand, best, best_index)) {
+#pragma unroll
+      for (int k = 0; k < kMinLimbs; ++k) best[k] = env.obj[k];
+      best_index = cand;
+    }
+    const u64 nvalid = (u64)__popcll(__ballot(valid));
+    evals += nvalid;
+    lsteps += nvalid * env.dsteps.steps;
+    lfull += nvalid * env.dsteps.full;
+    lshort += nvalid * env.dsteps.shrt;
+    lgen += nvalid * env.dsteps.gen;
+  }
+  if (lane == 0 && evals) {
+    atomicAdd((unsigned long long*)counter, (unsigned long long)evals);
+    if (lsteps) atomicAdd((unsigned long long*)(counter + 1), (unsigned long long)lsteps);
+    if (lfull) atomicAdd((unsigned long long*)(counter + 2), (unsigned long long)lfull);
+    if (lshort) atomicAdd((unsigned long long*)(counter + 3), (unsigned long long)lshort);
+    if (lgen) atomicAdd((unsigned long long*)(counter + 4), (unsigned long long)lgen);
+  }
+  min_block_reduce(best, best_index, lds_spill);
+  if (threadIdx.x == 0) min_write(records + blockIdx.x, best, best_index);
+}
+
+// The n block records of mw_search_min_kernel reduced to the call's, by one
+// block, queued behind it on the same stream.
+__global__ __launch_bounds__(kBlock) void mw_min_reduce_kernel(const MinRecord* __restrict__ records, u32 n,
+                                                                MinRecord* __restrict__ out) {
+  __shared__ u32 red[kMinReduceBytes / sizeof(u32)];
+  u32 best[kMinLimbs];
+  u64 best_index;
+  min_none(best, best_index);
+  for (u32 i = threadIdx.x; i < n; i += kBlock) {
+    const u64 oi = records[i].index;
+    u32 o[kMinLimbs];
+#pragma unroll
+    for (int k = 0; k < kMinLimbs; ++k) o[k] = records[i].obj[k];
+    if (oi != kMinNone && min_less(o, oi, best, best_index)) {
+#pragma unroll
+      for (int k = 0; k < kMinLimbs; ++k) best[k] = o[k];
+      best_index = oi;
+    }
+  }
+  min_block_reduce(best, best_index, red);
+  if (threadIdx.x == 0) min_write(out, best, best_index);
 }
 
 // Threaded-dispatch interpreter (mythril_amd/asmgen.py -> mw_asm_interp.inc):
@@ -1045,6 +1196,10 @@ int mg_init(int device, mg_ctx** out) {
           hipSuccess ||
       hipFuncSetAttribute((const void*)mw_eval_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) !=
           hipSuccess ||
+      hipFuncSetAttribute((const void*)mw_search_min_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                          lds_max) != hipSuccess ||
+      hipFuncSetAttribute((const void*)mw_search_min_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                          lds_max) != hipSuccess ||
       hipFuncSetAttribute((const void*)mw_search_asm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)(wide_lds_words() * kBlock * sizeof(u32))) != hipSuccess ||
       hipFuncSetAttribute((const void*)mw_search_asm_kernel_n, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) !=
@@ -1566,6 +1721,84 @@ int mg_search_begin(mg_ctx* h, mg_prog* const* hprogs, size_t nprog, uint64_t se
   }
   P.active = true;
   c->pending = std::move(P);
+  return 0;
+}
+
+// Plan and enqueue mg_search_min's launches (the context's mu held): the
+// launch records upload (zeroed counters, the program's record), the min
+// kernel, the records' reduction, and the readbacks of the counters and of the
+// call's record into the pinned buffer.  The records come from the context's
+// pool (rec), sized by the plan.  Nothing here waits for the device.
+static int search_min_enqueue(Ctx* c, const Prog* p, uint64_t seed, uint64_t begin, uint64_t count,
+                              const MinPlan& M, Scratch& rec) {
+  int rc = ensure_launch(c, 1, 0);
+  if (rc) return rc;
+  rc = ensure_spill(c, M.spill_need);
+  if (rc) return rc;
+  if (!rec.p) return fail(MG_E_NOMEM, "mg_search_min: record buffer");
+  if (!ensure_readback(c, sizeof(MinRecord))) return fail(MG_E_NOMEM, "mg_search_min: readback buffer");
+  MinRecord* d_rec = (MinRecord*)rec.p;
+  HIPCHK(stage_upload(c, 1, &p->dev, 1, nullptr, 0));
+  HIPCHK(hipEventRecord(c->e0, c->stream));
+  const auto kernel = M.pool_lds ? mw_search_min_kernel<true> : mw_search_min_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((u32)M.gx), dim3(kBlock), M.lds_bytes, c->stream, (const ProgDev*)c->d_progs, seed,
+                     begin, count, d_rec, c->d_counter, c->d_spill, M.nlds);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(mw_min_reduce_kernel, dim3(1), dim3(kBlock), 0, c->stream, (const MinRecord*)d_rec, (u32)M.gx,
+                     d_rec + M.gx);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->e1, c->stream));
+  HIPCHK(stage_readback(c, 1));   // the counters
+  HIPCHK(hipMemcpyAsync(c->h_rb, d_rec + M.gx, sizeof(MinRecord), hipMemcpyDeviceToHost, c->stream));
+  return 0;
+}
+
+int mg_search_min(mg_ctx* h, mg_prog* hp, uint64_t seed, uint64_t begin, uint64_t count, mg_min_result* out,
+                  mg_stats* st) {
+  if (!h || !hp || !out) return fail(MG_E_ARG, "null argument");
+  if (count == 0 || begin + count < begin) return fail(MG_E_ARG, "bad candidate range");
+  const u64 id = hid(hp);
+  mw::CallMark mark("mg_search_min");
+  mark.step("lock", count);
+  CallG call;
+  if (const char* why = mw::enter(g_reg, hid(h), &id, 1, call)) return fail(MG_E_ARG, std::string("mg_search_min: ") + why);
+  if (call.c->pending.active) return fail(MG_E_ARG, "mg_search_min: a search begun with mg_search_begin is pending");
+  Ctx* c = call.c.get();
+  const Prog* p = call.ps[0].get();
+  if (p->desc.n_trace_rows == 0 || p->desc.n_trace_rows > (u32)kMinLimbs)
+    return fail(MG_E_ARG, "mg_search_min: the objective is the program's trace rows: 1 to 8 of them");
+  mark.step("plan");
+  const double t0 = now_ms();
+  HIPCHK(hipSetDevice(c->dev));
+  (void)hipGetLastError();  // start from a clean error state: launch errors are read back below
+  const MinPlan M = plan_search_min(facts_of(p), count, c->ncu);
+  mark.step("enqueue", count);
+  Scratch rec(c, M.record_bytes);
+  int rc = search_min_enqueue(c, p, seed, begin, count, M, rec);
+  if (rc) return rc;   // (rec waits for the stream before its buffer goes back to the pool)
+  mark.step("sync", count);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  rec.synced = true;
+  c->uploads_landed();   // the stream drained: a queued program upload has landed
+  c->eu_live = false;
+  std::memcpy(out, c->h_rb, sizeof(MinRecord));
+  if (st) {
+    const u64* stripes = (const u64*)c->h_blk;
+    u64 ctr[kNCounters] = {0, 0, 0, 0, 0};
+    for (size_t sidx = 0; sidx <= MW_CTR_STRIPES; ++sidx)
+      for (int k = 0; k < kNCounters; ++k) ctr[k] += stripes[sidx * MW_CTR_STRIPE_WORDS + k];
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1));
+    st->kernel_ms = ms;
+    st->wall_ms = now_ms() - t0;
+    st->evals = ctr[0];
+    st->launches = 2;
+    st->ops = (double)ctr[0] * (double)p->ops_per_eval;
+    st->lane_div_steps = ctr[1];
+    st->lane_div_full = ctr[2];
+    st->lane_div_short = ctr[3];
+    st->lane_div_general = ctr[4];
+  }
   return 0;
 }
 

@@ -214,4 +214,40 @@ inline SearchPlan plan_search(const ProgFacts* facts, size_t n, u64 count, int n
   return S;
 }
 
+// mg_search_min: one program on the compiled interpreter's min kernel
+// (mw_search_min_kernel), whatever engine a plain search gives it.  Every
+// block writes one record {u64 index, u32 obj[8]} and a one-block kernel
+// reduces them, so grid x is capped: the record buffer stays small.
+constexpr u64 kMinMaxBlocks = 4096;
+constexpr size_t kMinRecordBytes = 40;
+// the block's four wave records meet in LDS, in the spill rows (dead by then)
+constexpr size_t kMinReduceBytes = (kBlock / 64) * kMinRecordBytes;
+
+struct MinPlan {
+  u64 gx = 1;              // blocks, and records
+  u32 nlds = 0;            // spill words in LDS
+  bool pool_lds = false;   // the pool is staged in LDS
+  size_t lds_bytes = 0;    // dynamic LDS of the launch
+  size_t spill_need = 4;   // bytes of global spill buffer
+  size_t record_bytes = 0; // the blocks' records, then the call's
+};
+
+// The LDS split is plan_search's rule for the compiled interpreter's group
+// (the running best stays in registers: the kernel has no scratch with it,
+// tests/test_search_min_build.py); the launch gets at least the room the
+// block's reduction needs.
+inline MinPlan plan_search_min(const ProgFacts& f, u64 count, int ncu) {
+  MinPlan M;
+  const u64 nchunks = (count + kBlock - 1) / kBlock;
+  M.gx = std::max<u64>(1, std::min<u64>({nchunks, (u64)ncu * 8, kMinMaxBlocks}));
+  M.nlds = std::min(f.n_spill, kLdsSpillWords);
+#ifndef MW_NO_POOL_LDS
+  M.pool_lds = f.npool && asm_lds_bytes(M.nlds, f.npool) <= (size_t)kLdsSpillWords * kBlock * 4;
+#endif
+  M.lds_bytes = std::max(asm_lds_bytes(M.nlds, M.pool_lds ? f.npool : 0), kMinReduceBytes);
+  M.spill_need = std::max<size_t>(4, (size_t)(f.n_spill - M.nlds) * M.gx * kBlock * sizeof(u32));
+  M.record_bytes = (size_t)(M.gx + 1) * kMinRecordBytes;
+  return M;
+}
+
 }  // namespace mw

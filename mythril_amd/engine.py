@@ -54,6 +54,7 @@ class Witness:
     values: Dict[str, int]                           # every scalar leaf (incl. Ackermann leaves)
     arrays: Dict[str, Dict[int, int]] = field(default_factory=dict)
     functions: Dict[str, Dict[Tuple[int, ...], int]] = field(default_factory=dict)
+    objective: Optional[int] = None                  # search_min: the objective's value at index
 
 
 @dataclass
@@ -514,6 +515,23 @@ def _witness_program(prog: Program, traced: List[Node]) -> Program:
     return compile_query([], leaf_specs=fixed, trace=traced)
 
 
+def _objective_program(q: "Query", objective: Node) -> Program:
+    """search_min's program: q's conjuncts with `objective` traced (a narrow
+    one through STORE_N, one row; a wide one through STORE_W, eight), on
+    q.program's leaf layout as _witness_program keeps it (the pool fields
+    already assigned), so that candidate i is the assignment q.program
+    checks at i."""
+    from .runtime import EngineError
+    fixed = {s.name: dataclasses.replace(s, pool=None if s.pool is None else list(s.pool))
+             for s in q.program.leaf_specs}
+    p = compile_query(q.lowered.conjuncts, leaf_specs=fixed, trace=[objective])
+    n = len(q.program.leaf_nodes)
+    if not _same_leaves(q, p) or not np.array_equal(p.leaves[:8 * n], q.program.leaves[:8 * n]):
+        # an EngineError, so the drop-in's handlers send the query to z3
+        raise EngineError("objective program's leaf layout differs from the search program's")
+    return p
+
+
 def _combine_chunks(values: Dict[str, int], name: str, width: int) -> int:
     if name in values:
         return values[name]
@@ -629,6 +647,44 @@ class WitnessEngine:
             if prof is not None:
                 _tick(prof, "free", t0)
         return out
+
+    def search_min(self, q: Query, objective: Node, count: Optional[int] = None,
+                   begin: int = 0) -> Optional[Witness]:
+        """The witness of ``q`` among candidates [begin, begin+count) whose
+        ``objective`` (a term of q's context, at most 256 bits, compared
+        unsigned) is smallest, ties to the lowest index; None when no
+        candidate satisfies.  One launch evaluates the whole range
+        (mg_search_min, always on the compiled interpreter): q's conjuncts
+        compiled with the objective traced, on q.program's leaf layout, so
+        the candidates are those ``search`` draws.  The witness is
+        materialised at the returned index as ``search`` does it, with the
+        objective's value in ``Witness.objective``; like every witness it is
+        not re-evaluated here (the drop-in re-checks it with z3).  To
+        maximise a term t, pass ``bvnot(t)``: the smallest complement is the
+        largest t.  Raises Unsupported for an objective wider than 256 bits."""
+        width = 1 if objective.width == BOOL else objective.width
+        if width > isa.MAX_WIDTH:
+            raise Unsupported(f"objective of {width} bits: at most {isa.MAX_WIDTH}")
+        p = _objective_program(q, objective)
+        count = count or self.launch_count([q])
+        dp = self.dev.load(p)
+        try:
+            idx, value, st = self.dev.search_min(dp, self.seed, begin, count)
+            self.stats["searches"] += 1
+            self.stats["programs"] += 1
+            self.stats["evals"] += st["evals"]
+            self.stats["kernel_ms"] += st["kernel_ms"]
+            if idx is None:
+                return None
+            # the leaf values come from this program when its leaf table is q.program's
+            same = len(p.leaf_nodes) == len(q.program.leaf_nodes)
+            w = self.materialize(q, idx, dp if same else None)
+            if w is not None:
+                w.objective = value
+                self.stats["hits"] += 1
+            return w
+        finally:
+            dp.free()
 
     def _assemble(self, dps) -> None:
         """Attach assembled kernels to the eligible programs (parallel

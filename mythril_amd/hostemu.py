@@ -17,7 +17,7 @@ from typing import Callable, List, Sequence
 import numpy as np
 
 from .compiler import Program, compile_program
-from .runtime import MgProgDesc, make_desc, unpack_trace
+from .runtime import MgMinResult, MgProgDesc, make_desc, unpack_trace
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST_EMU = os.path.join(ROOT, "build", "host", "libmw_host_emu.so")
@@ -37,9 +37,26 @@ def lib():
         L.mwh_div_counts.restype = ctypes.c_int
         L.mwh_div_counts.argtypes = [ctypes.POINTER(MgProgDesc), ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t,
                                      ctypes.c_void_p]
+        L.mwh_search_min.restype = ctypes.c_int
+        L.mwh_search_min.argtypes = [ctypes.POINTER(MgProgDesc), ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                     ctypes.POINTER(MgMinResult)]
         L.mg_last_error.restype = ctypes.c_char_p
         _lib = L
     return _lib
+
+
+def search_min(p: Program, seed: int, begin: int, n: int):
+    """(index, objective) of the witness among generated candidates
+    [begin, begin+n) whose objective (p's trace rows, 1 to 8 limbs, least
+    significant first) is lowest, ties to the lowest index; (None, 0) without
+    one.  The host twin of mg_search_min: the same mw_run and the same order
+    (csrc/mw_min.h), one candidate after the other."""
+    d, keep = make_desc(p)
+    out = MgMinResult()
+    rc = lib().mwh_search_min(ctypes.byref(d), seed & ((1 << 64) - 1), begin, n, ctypes.byref(out))
+    if rc != 0:
+        raise RuntimeError(lib().mg_last_error().decode())
+    return out.decode()
 
 
 def eval_generated(p: Program, seed: int, begin: int, n: int):

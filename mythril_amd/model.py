@@ -224,6 +224,9 @@ def _gpu_model(constraints, timeout):
 PINNED_CHECK_MS = int(os.environ.get("MYTHRIL_AMD_PINNED_CHECK_MS", "250"))
 MINIMIZE_HINTS = os.environ.get("MYTHRIL_AMD_MINIMIZE_HINTS", "0") == "1"
 MINIMIZE_ROUNDS = int(os.environ.get("MYTHRIL_AMD_MINIMIZE_ROUNDS", "8"))   # device descent searches
+# how the hint's bound is found: "descent" (a first witness, then MINIMIZE_ROUNDS
+# searches below it), or "device": one objective-minimising launch (mg_search_min)
+MINIMIZE_MODE = os.environ.get("MYTHRIL_AMD_MINIMIZE_MODE", "descent")
 
 
 def _walk(roots):
@@ -242,7 +245,11 @@ def _minimize_hint(constraints, minimize, timeout):
     satisfies it), only prune z3's search.  The bound is tightened by up to
     MINIMIZE_ROUNDS more searches with ``obj_0 <=u target`` added, the target
     halving the gap to the lowest value not yet ruled out by a miss (a miss
-    proves nothing, it only moves the target up).  Later objectives get no bound (the
+    proves nothing, it only moves the target up).  With
+    ``MYTHRIL_AMD_MINIMIZE_MODE=device`` the first search and the descent are one
+    objective-minimising search instead (``WitnessEngine.search_min``): the
+    lowest ``obj_0`` among the witnesses of the candidates one launch draws;
+    the z3 confirmation is the same.  Later objectives get no bound (the
     witness need not be optimal in obj_0, so its later values bound nothing in
     the lexicographic order).  The optimum is preserved, but z3 may return a
     different model with the same objective values, i.e. different transaction
@@ -277,26 +284,40 @@ def _minimize_hint(constraints, minimize, timeout):
         script = z3bridge.to_ir(raws)
         from .engine import prepare
         q = prepare(script.asserts, script.ctx)
-        w = eng.search([q])[0]
-        if w is None or name not in w.values or not confirmed(w):
-            return None
-        best = w.values[name]
-        # descent: search again below the best value so far, aiming at half of
-        # it first (each round adds obj_0 <u target; a miss proves nothing, so
-        # the target moves back up towards the best witness)
-        var = next((n for n in _walk(script.asserts) if n.op == "var" and n.name == name), None)
-        lo = 0
-        for _ in range(MINIMIZE_ROUNDS if var is not None else 0):
-            if best <= lo:
-                break
-            target = lo + (best - lo) // 2
-            extra = script.ctx.app("bvule", var, script.ctx.const(target, var.width))
-            w2 = eng.search([prepare(list(script.asserts) + [extra], script.ctx)])[0]
-            if w2 is not None and name in w2.values and w2.values[name] <= target and confirmed(w2):
-                best = w2.values[name]
-            else:
-                lo = target + 1
-        STATS["minimize_rounds"] = STATS.get("minimize_rounds", 0) + 1
+        if MINIMIZE_MODE == "device" and hasattr(eng.dev, "search_min"):
+            # one exhaustive launch over the candidates the first search would
+            # draw, reduced by obj_0 on the device (WitnessEngine.search_min):
+            # the lowest obj_0 among their witnesses, where the descent below
+            # prepares, uploads and searches up to MINIMIZE_ROUNDS more queries
+            var = next((n for n in _walk(script.asserts) if n.op == "var" and n.name == name), None)
+            if var is None:
+                return None
+            STATS["minimize_device"] = STATS.get("minimize_device", 0) + 1
+            w = eng.search_min(q, var)
+            if w is None or name not in w.values or not confirmed(w):
+                return None
+            best = w.values[name]
+        else:
+            w = eng.search([q])[0]
+            if w is None or name not in w.values or not confirmed(w):
+                return None
+            best = w.values[name]
+            # descent: search again below the best value so far, aiming at half of
+            # it first (each round adds obj_0 <u target; a miss proves nothing, so
+            # the target moves back up towards the best witness)
+            var = next((n for n in _walk(script.asserts) if n.op == "var" and n.name == name), None)
+            lo = 0
+            for _ in range(MINIMIZE_ROUNDS if var is not None else 0):
+                if best <= lo:
+                    break
+                target = lo + (best - lo) // 2
+                extra = script.ctx.app("bvule", var, script.ctx.const(target, var.width))
+                w2 = eng.search([prepare(list(script.asserts) + [extra], script.ctx)])[0]
+                if w2 is not None and name in w2.values and w2.values[name] <= target and confirmed(w2):
+                    best = w2.values[name]
+                else:
+                    lo = target + 1
+            STATS["minimize_rounds"] = STATS.get("minimize_rounds", 0) + 1
     except (Unsupported, RecursionError, ValueError, KeyError, EngineError):
         return None
     from mythril.laser.smt import UGE, symbol_factory

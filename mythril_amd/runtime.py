@@ -54,6 +54,17 @@ class MgStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class MgMinResult(ctypes.Structure):
+    """include/mythril_witness.h mg_min_result"""
+    _fields_ = [("index", ctypes.c_uint64), ("value", ctypes.c_uint32 * 8)]
+
+    def decode(self) -> Tuple[Optional[int], int]:
+        """(index or None, the objective as an integer)"""
+        if self.index == MG_NONE:
+            return None, 0
+        return int(self.index), sum(int(v) << (32 * k) for k, v in enumerate(self.value))
+
+
 _P = ctypes.c_void_p
 _lib = None
 _lib_lock = threading.Lock()
@@ -76,6 +87,8 @@ SIGNATURES = {
     "mg_search_end": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(MgStats),
                                      ctypes.POINTER(ctypes.POINTER(MgProgDesc)), ctypes.POINTER(_P),
                                      ctypes.POINTER(ctypes.c_int32)]),
+    "mg_search_min": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                     ctypes.POINTER(MgMinResult), ctypes.POINTER(MgStats)]),
     "mg_eval": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t, _P, _P]),
     "mg_eval_generated": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t, _P, _P]),
     "mg_witness_leaves": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, _P]),
@@ -250,6 +263,20 @@ class Device:
                                             flags, out, ctypes.byref(st)), "mg_search")
         res = [None if v == MG_NONE else int(v) for v in out]
         return res, st.as_dict()
+
+    def search_min(self, dp: DeviceProgram, seed: int, begin: int,
+                   count: int) -> Tuple[Optional[int], int, dict]:
+        """mg_search_min: (index, objective, stats) of the witness in
+        [begin, begin+count) whose objective (dp's trace rows, 1 to 8 limbs)
+        is lowest, ties to the lowest index; (None, 0, stats) without one."""
+        if self._reap_queue:
+            self._reap()
+        out = MgMinResult()
+        st = MgStats()
+        _check(self.lib, self.lib.mg_search_min(self.handle, dp.handle, seed & ((1 << 64) - 1), begin, count,
+                                                ctypes.byref(out), ctypes.byref(st)), "mg_search_min")
+        idx, val = out.decode()
+        return idx, val, st.as_dict()
 
     def search_begin(self, progs: Sequence[DeviceProgram], seed: int, begin: int, count: int,
                      flags: int = 0) -> None:
