@@ -145,6 +145,38 @@ typedef struct { uint64_t index; uint32_t value[8]; } mg_min_result;
 int mg_search_min(mg_ctx* ctx, mg_prog* prog, uint64_t seed, uint64_t begin,
                   uint64_t count, mg_min_result* out, mg_stats* stats);
 
+typedef struct { uint32_t row, nrows; } mg_lex_obj;
+typedef struct { uint64_t index; uint32_t value[8][8]; } mg_lex_result;   /* value[k]: objective k's limbs */
+/* Lexicographic minimum over several objectives among the witnesses of
+ * candidates [begin, begin+count).  Objective k is the program's trace rows
+ * [objs[k].row, objs[k].row + objs[k].nrows), 1..8 limbs, least significant
+ * first, one unsigned value; objs[0] has the highest priority; every objective
+ * equal: the lowest index.  Two objectives may name the same rows, and rows
+ * need not follow the priority order.  The range is cut into tiles of `tile`
+ * candidates (a multiple of 256; 0: the default; cut further so that one
+ * tile's verdicts and trace rows fit 64 MiB).  Each tile is evaluated with its
+ * trace rows on the engine mg_eval_generated uses when a trace is asked for
+ * (the asm interpreter where it runs the program, else the compiled one; an
+ * attached specialised or assembled kernel is not used), then folded into a
+ * running minimum on the device: stats->launches == 2 * tiles + 1,
+ * stats->evals == count, one synchronisation.  out->index = MG_NONE (and value
+ * all zero) when no candidate satisfies.  Refused with MG_E_ARG for nobj of 0
+ * or above 8, nrows of 0 or above 8, rows outside the program's trace, count
+ * == 0 or a wrapping range, a tile that is no multiple of 256, more than
+ * 65536 tiles, and while a search begun with mg_search_begin is pending.
+ * Same handle, lock and in-flight protocol as mg_search_min.  Replaces
+ * Optimize.minimize over the whole objective tuple + check
+ * (mythril/laser/smt/solver/solver.py:109-114 and :51-66, reached from
+ * mythril/analysis/solver.py:51-68 and :216-256, which minimises
+ * (calldatasize, callvalue) per transaction lexicographically): a bound from
+ * one pass over the candidates, not the optimum over all assignments. */
+int mg_search_lexmin(mg_ctx* ctx, mg_prog* prog, uint64_t seed, uint64_t begin, uint64_t count,
+                     const mg_lex_obj* objs, size_t nobj, uint64_t tile, mg_lex_result* out, mg_stats* stats);
+/* The tile mg_search_lexmin cuts a range of `count` candidates of this
+ * program into when asked for `tile`, in *out.  Replaces nothing in the
+ * reference: a diagnostic for tests and benchmarks. */
+int mg_search_lexmin_tile(mg_ctx* ctx, mg_prog* prog, uint64_t count, uint64_t tile, uint64_t* out);
+
 /* Evaluate one program on explicit assignments: leaves_soa has n_input_rows
  * rows of ncand u32 (row r, candidate i at [r*ncand + i]).  verdict[i] = 0/1;
  * trace (may be NULL) receives n_trace_rows rows of ncand u32. */

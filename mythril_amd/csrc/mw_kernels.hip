@@ -36,6 +36,7 @@
 #include "mw_keccak.h"
 #include "mw_launch_plan.h"
 #include "mw_leaf.h"
+#include "mw_lex.h"
 #include "mw_min.h"
 
 extern "C" int mw_fail(int code, const char* msg);
@@ -394,6 +395,83 @@ __global__ __launch_bounds__(kBlock) void mw_min_reduce_kernel(const MinRecord* 
   }
   min_block_reduce(best, best_index, red);
   if (threadIdx.x == 0) min_write(out, best, best_index);
+}
+
+namespace {
+
+constexpr u32 kLexNoOffset = ~0u;   // a thread, wave or block that has met no witness
+
+// The block's best of the threads' `best` (tile offsets or record numbers,
+// kLexNoOffset: none), in thread 0: a butterfly over each wave, then the
+// waves' values through red[kBlock / 64]; before(a, b) says whether a comes
+// first (both not kLexNoOffset), by reading memory.
+template <class Before>
+__device__ __forceinline__ u32 lex_block_reduce(u32 best, u32* red, Before before) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+    const u32 o = __shfl_xor(best, m);
+    if (o != kLexNoOffset && (best == kLexNoOffset || before(o, best))) best = o;
+  }
+  if ((threadIdx.x & 63u) == 0u) red[threadIdx.x >> 6] = best;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (u32 w = 1; w < kBlock / 64; ++w) {
+      const u32 o = red[w];
+      if (o != kLexNoOffset && (best == kLexNoOffset || before(o, best))) best = o;
+    }
+  return best;
+}
+
+}  // namespace
+
+// mg_search_lexmin's tile fold: the n candidates of one evaluated tile
+// (verdict[j]; row r of tile offset j at trace[r * stride + j]; candidate
+// index base + j) folded into records[blockIdx.x], this block's running
+// minimum over the tiles of the call in the order of mw_lex.h.  A thread keeps
+// only the tile offset of its best candidate and compares by reading rows, so
+// the key's length costs no register; offsets ascend and the compare is
+// strict, so ties stay with the lowest index.  A candidate of verdict 0 never
+// competes.  The grid is the same for every tile of a call and the tiles'
+// folds follow each other on one stream: thread 0 compares and overwrites its
+// block's record with plain stores.  objs is read from device memory (uniform
+// loads: an array indexed at run time in the kernel's arguments would go to scratch).
+__global__ __launch_bounds__(kBlock) void mw_lex_fold_kernel(const u32* __restrict__ verdict,
+                                                              const u32* __restrict__ trace, u64 stride, u32 n,
+                                                              u64 base, const LexObj* __restrict__ objs, u32 nobj,
+                                                              u32* __restrict__ records, u32 record_words) {
+  __shared__ u32 red[kBlock / 64];
+  u32 best = kLexNoOffset;
+  for (u64 j = (u64)blockIdx.x * kBlock + threadIdx.x; j < n; j += (u64)gridDim.x * kBlock)
+    if (verdict[j] && (best == kLexNoOffset || lex_less(trace, stride, j, j, best, best, objs, nobj))) best = (u32)j;
+  best = lex_block_reduce(best, red, [&](u32 a, u32 b) { return lex_less(trace, stride, a, a, b, b, objs, nobj); });
+  if (threadIdx.x == 0 && best != kLexNoOffset) {
+    u32* rec = records + (u64)blockIdx.x * record_words;
+    if (lex_less(trace, stride, best, base + best, rec, objs, nobj)) lex_store(rec, trace, stride, best, base + best, objs, nobj);
+  }
+}
+
+// The n block records of the folds reduced to the call's, in the same order,
+// by one block queued after the last fold.  A record still at MG_NONE never
+// competes; without any witness the result is MG_NONE with a zero key.
+__global__ __launch_bounds__(kBlock) void mw_lex_reduce_kernel(const u32* __restrict__ records, u32 n,
+                                                                const LexObj* __restrict__ objs, u32 nobj,
+                                                                u32 record_words, u32* __restrict__ out) {
+  __shared__ u32 red[kBlock / 64];
+  auto before = [&](u32 a, u32 b) {
+    return lex_less_records(records + (u64)a * record_words, records + (u64)b * record_words, objs, nobj);
+  };
+  u32 best = kLexNoOffset;
+  for (u32 i = threadIdx.x; i < n; i += kBlock)
+    if (lex_record_index(records + (u64)i * record_words) != kLexNone && (best == kLexNoOffset || before(i, best))) best = i;
+  best = lex_block_reduce(best, red, before);
+  if (threadIdx.x == 0) {
+    if (best == kLexNoOffset) {
+      for (u32 k = 0; k < record_words; ++k) out[k] = k < kLexRecordHead ? ~0u : 0u;
+    } else {
+      const u32* src = records + (u64)best * record_words;
+      for (u32 k = 0; k < record_words; ++k) out[k] = src[k];
+    }
+  }
 }
 
 // Threaded-dispatch interpreter (mythril_amd/asmgen.py -> mw_asm_interp.inc):
@@ -1950,6 +2028,33 @@ int mg_search_end(mg_ctx* h, uint64_t* out_min_idx, mg_stats* st, const mg_prog_
   return rc;
 }
 
+// The launch part of an evaluation of generated or given candidates, shared by
+// mg_eval / mg_eval_generated (eval_common, eval_asm) and the tiles of
+// mg_search_lexmin.  On the compiled interpreter: ncand candidates from
+// `begin` (or the rows at d_in), verdicts at d_v, trace rows (or null) at d_t.
+static hipError_t launch_eval_compiled(Ctx* c, const Prog* p, const u32* d_in, u64 ncand, u64 seed, u64 begin,
+                                       u32* d_v, u32* d_t, u64 gx, u32 nlds) {
+  hipLaunchKernelGGL(mw_eval_kernel, dim3((u32)gx), dim3(kBlock), (size_t)nlds * kBlock * 4, c->stream,
+                     p->dev, d_in, ncand, seed, begin, d_v, d_t, c->d_spill, nlds);
+  return hipGetLastError();
+}
+
+// On an asm engine: the launch record of `count` generated candidates from
+// `begin` (verdicts at d_v, trace rows or null at d_t, row stride count), and
+// the launch on a record at dargs with the program's record at c->d_progs.
+static AsmArgs eval_asm_args(Ctx* c, u64 seed, u64 begin, u64 count, u64 gx, u32 nlds, u32* d_v, u32* d_t) {
+  AsmArgs aa = asm_args<AsmArgs>(seed, begin, count, 0, gx, nlds, 0, c->d_spill);
+  aa.verdict = d_v;
+  aa.trace = d_t;
+  aa.ncand = (u32)count;
+  return aa;
+}
+
+static int launch_eval_asm(Ctx* c, const Prog* p, bool assembled, const AsmArgs* dargs, u64 gx, u32 nlds) {
+  return launch_asm(c, assembled ? p->afn : nullptr, p->asm_layout, c->d_progs, dargs, c->d_min, c->d_counter, gx,
+                    nlds, p->dev.npool);
+}
+
 static int eval_common(Ctx* c, const Prog* p, const uint32_t* leaves_soa, size_t ncand, uint64_t seed,
                        uint64_t begin, uint32_t* verdict, uint32_t* trace) {
   if (!verdict || ncand == 0) return fail(MG_E_ARG, "null argument");
@@ -1971,9 +2076,8 @@ static int eval_common(Ctx* c, const Prog* p, const uint32_t* leaves_soa, size_t
   if (nin && hipMemcpyAsync(d_in, leaves_soa, nin * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess)
     return fail(MG_E_HIP, "eval input copy");
   if (ntr && !p->trace_full) hipMemsetAsync(d_t, 0, tb, c->stream);
-  hipLaunchKernelGGL(mw_eval_kernel, dim3((u32)gx), dim3(kBlock), (size_t)nlds * kBlock * 4, c->stream,
-                     p->dev, (const u32*)d_in, (u64)ncand, seed, begin, d_v, d_t, c->d_spill, nlds);
-  const hipError_t e = eval_readback(c, hipGetLastError(), "eval/sync", d_v, vb, tb, verdict, trace);
+  const hipError_t e = eval_readback(c, launch_eval_compiled(c, p, d_in, ncand, seed, begin, d_v, d_t, gx, nlds),
+                                     "eval/sync", d_v, vb, tb, verdict, trace);
   s_in.synced = s_vt.synced = e == hipSuccess;
   if (e != hipSuccess) return fail(MG_E_HIP, std::string("eval: ") + hipGetErrorString(e));
   return 0;
@@ -2029,15 +2133,11 @@ static int eval_asm(Ctx* c, const Prog* p, uint64_t seed, uint64_t begin, size_t
   Scratch s_v(c, vb + tb);
   if (!s_v.p) return fail(MG_E_NOMEM, "eval verdict alloc");
   u32 *d_v = s_v.u(), *d_t = ntr ? d_v + count : nullptr;
-  AsmArgs aa = asm_args<AsmArgs>(seed, begin, count, 0, gx, nlds, 0, c->d_spill);
-  aa.verdict = d_v;
-  aa.trace = d_t;
-  aa.ncand = (u32)count;
+  const AsmArgs aa = eval_asm_args(c, seed, begin, count, gx, nlds, d_v, d_t);
   hipError_t e = ntr && !p->trace_full ? hipMemsetAsync(d_t, 0, tb, c->stream) : hipSuccess;
   if (e == hipSuccess) e = stage_upload(c, 1, assembled ? &p->dev : &p->adev, 1, &aa, 1);
   if (e == hipSuccess) {
-    rc = launch_asm(c, assembled ? p->afn : nullptr, p->asm_layout, c->d_progs, c->d_asmargs, c->d_min, c->d_counter,
-                    gx, nlds, p->dev.npool);
+    rc = launch_eval_asm(c, p, assembled, c->d_asmargs, gx, nlds);
     if (rc) return rc;
   }
   e = eval_readback(c, e, "eval_asm/sync", d_v, vb, tb, verdict, trace);
@@ -2083,6 +2183,141 @@ int mg_eval_generated(mg_ctx* h, const mg_prog* hp, uint64_t seed, uint64_t begi
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   s_v.synced = e == hipSuccess;
   if (e != hipSuccess) return fail(MG_E_HIP, std::string("eval (specialised): ") + hipGetErrorString(e));
+  return 0;
+}
+
+// the plan of an mg_search_lexmin of this program (mw_launch_plan.h)
+static LexPlan lexmin_plan(const Ctx* c, const Prog* p, u64 count, u64 tile, u32 key_words) {
+  return plan_search_lexmin(facts_of(p), count, tile, key_words, p->desc.n_trace_rows, c->ncu, asm_enabled(),
+                            wide_lds_words());
+}
+
+// Enqueue mg_search_lexmin's work (the context's mu held).  Every buffer is
+// sized first: spill, the launch block (one AsmArgs record per tile on the asm
+// interpreter, and one more record's room that carries the objectives), the
+// tile's verdict and trace block (vt) and the records (rec) from the pool.
+// Then, on the stream: one upload, the records set to MG_NONE, per tile the
+// evaluation and the fold, the reduction, the readbacks.  Between the first
+// launch and the caller's synchronisation nothing allocates, frees or waits.
+static int search_lexmin_enqueue(Ctx* c, const Prog* p, uint64_t seed, uint64_t begin, uint64_t count,
+                                 const LexObj* objs, u32 nobj, const LexPlan& L, Scratch& vt, Scratch& rec) {
+  static_assert(sizeof(AsmArgs) >= kLexMaxObj * sizeof(LexObj), "the objectives travel in one AsmArgs record's room");
+  const bool on_asm = L.engine.kind == kAsm;
+  const size_t ntile_args = on_asm ? (size_t)L.ntiles : 0;
+  int rc = ensure_launch(c, 1, ntile_args + 1);
+  if (rc) return rc;
+  rc = ensure_spill(c, L.spill_need);
+  if (rc) return rc;
+  if (!vt.p || !rec.p) return fail(MG_E_NOMEM, "mg_search_lexmin: tile and record buffers");
+  const size_t rec_bytes = (size_t)L.record_words * sizeof(u32);
+  if (!ensure_readback(c, rec_bytes)) return fail(MG_E_NOMEM, "mg_search_lexmin: readback buffer");
+  u32 *d_v = vt.u(), *d_t = d_v + L.tile, *d_rec = rec.u();
+  const u32 nrows = p->desc.n_trace_rows;
+  auto tile_n = [&](u64 t) { return std::min<u64>(L.tile, count - t * L.tile); };
+  auto tile_gx = [&](u64 n) { return std::min<u64>((n + kBlock - 1) / kBlock, L.eval_gx); };
+  std::vector<AsmArgs> ha(ntile_args + 1);
+  for (size_t t = 0; t < ntile_args; ++t)
+    ha[t] = eval_asm_args(c, seed, begin + t * L.tile, tile_n(t), tile_gx(tile_n(t)), L.nlds, d_v, d_t);
+  std::memset(&ha[ntile_args], 0, sizeof(AsmArgs));
+  std::memcpy(&ha[ntile_args], objs, nobj * sizeof(LexObj));
+  const LexObj* d_objs = (const LexObj*)(c->d_asmargs + ntile_args);
+  HIPCHK(stage_upload(c, 1, on_asm ? &p->adev : &p->dev, 1, ha.data(), ha.size()));
+  HIPCHK(hipMemsetAsync(d_rec, 0xff, L.record_bytes, c->stream));   // every record at MG_NONE
+  HIPCHK(hipEventRecord(c->e0, c->stream));
+  for (u64 t = 0; t < L.ntiles; ++t) {
+    const u64 n = tile_n(t), tb = begin + t * L.tile;
+    if (!p->trace_full) HIPCHK(hipMemsetAsync(d_t, 0, (size_t)nrows * n * 4, c->stream));
+    if (on_asm) {
+      rc = launch_eval_asm(c, p, false, c->d_asmargs + t, tile_gx(n), L.nlds);
+      if (rc) return rc;
+    } else {
+      HIPCHK(launch_eval_compiled(c, p, nullptr, n, seed, tb, d_v, d_t, tile_gx(n), L.nlds));
+    }
+    hipLaunchKernelGGL(mw_lex_fold_kernel, dim3((u32)L.fold_gx), dim3(kBlock), 0, c->stream, (const u32*)d_v,
+                       (const u32*)d_t, n, (u32)n, tb, d_objs, nobj, d_rec, L.record_words);
+    HIPCHK(hipGetLastError());
+  }
+  u32* d_out = d_rec + L.fold_gx * L.record_words;
+  hipLaunchKernelGGL(mw_lex_reduce_kernel, dim3(1), dim3(kBlock), 0, c->stream, (const u32*)d_rec, (u32)L.fold_gx,
+                     d_objs, nobj, L.record_words, d_out);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c->e1, c->stream));
+  HIPCHK(stage_readback(c, 1));   // the counters
+  HIPCHK(hipMemcpyAsync(c->h_rb, d_out, rec_bytes, hipMemcpyDeviceToHost, c->stream));
+  return 0;
+}
+
+int mg_search_lexmin(mg_ctx* h, mg_prog* hp, uint64_t seed, uint64_t begin, uint64_t count, const mg_lex_obj* objs,
+                     size_t nobj, uint64_t tile, mg_lex_result* out, mg_stats* st) {
+  static_assert(sizeof(mg_lex_obj) == sizeof(LexObj), "mg_lex_obj is a LexObj");
+  if (!h || !hp || !out || !objs) return fail(MG_E_ARG, "null argument");
+  if (count == 0 || begin + count < begin) return fail(MG_E_ARG, "bad candidate range");
+  if (nobj == 0 || nobj > (size_t)kLexMaxObj) return fail(MG_E_ARG, "mg_search_lexmin: 1 to 8 objectives");
+  if (tile % kBlock) return fail(MG_E_ARG, "mg_search_lexmin: the tile is a multiple of 256 candidates (0: the default)");
+  const u64 id = hid(hp);
+  mw::CallMark mark("mg_search_lexmin");
+  mark.step("lock", count);
+  CallG call;
+  if (const char* why = mw::enter(g_reg, hid(h), &id, 1, call)) return fail(MG_E_ARG, std::string("mg_search_lexmin: ") + why);
+  if (call.c->pending.active) return fail(MG_E_ARG, "mg_search_lexmin: a search begun with mg_search_begin is pending");
+  Ctx* c = call.c.get();
+  const Prog* p = call.ps[0].get();
+  LexObj key[kLexMaxObj];
+  for (size_t k = 0; k < nobj; ++k) {
+    key[k] = {objs[k].row, objs[k].nrows};
+    if (key[k].nrows == 0 || key[k].nrows > kLexMaxRows || key[k].row >= p->desc.n_trace_rows ||
+        key[k].nrows > p->desc.n_trace_rows - key[k].row)
+      return fail(MG_E_ARG, "mg_search_lexmin: an objective is 1 to 8 of the program's trace rows");
+  }
+  mark.step("plan");
+  const double t0 = now_ms();
+  HIPCHK(hipSetDevice(c->dev));
+  (void)hipGetLastError();  // start from a clean error state: launch errors are read back below
+  const LexPlan L = lexmin_plan(c, p, count, tile, lex_key_words(key, (u32)nobj));
+  if (!L.ntiles) return fail(MG_E_ARG, "mg_search_lexmin: more than 65536 tiles: a larger tile or a shorter range");
+  mark.step("enqueue", count);
+  Scratch vt(c, L.scratch_bytes), rec(c, L.record_bytes);
+  int rc = search_lexmin_enqueue(c, p, seed, begin, count, key, (u32)nobj, L, vt, rec);
+  if (rc) return rc;   // (the buffers wait for the stream before they go back to the pool)
+  mark.step("sync", count);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  vt.synced = rec.synced = true;
+  c->uploads_landed();   // the stream drained: a queued program upload has landed
+  c->eu_live = false;
+  const u32* r = (const u32*)c->h_rb;
+  std::memset(out, 0, sizeof(*out));
+  out->index = lex_record_index(r);
+  if (out->index != kLexNone) {
+    const u32* kw = r + kLexRecordHead;
+    for (size_t k = 0; k < nobj; kw += key[k].nrows, ++k)
+      for (u32 l = 0; l < key[k].nrows; ++l) out->value[k][l] = kw[l];
+  }
+  if (st) {
+    const u64* stripes = (const u64*)c->h_blk;
+    u64 evals = 0;
+    for (size_t sidx = 0; sidx <= MW_CTR_STRIPES; ++sidx) evals += stripes[sidx * MW_CTR_STRIPE_WORDS];
+    // (mw_eval_kernel counts nothing: it evaluates every candidate it is given)
+    if (L.engine.kind != kAsm) evals = count;
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1));
+    std::memset(st, 0, sizeof(*st));
+    st->kernel_ms = ms;
+    st->wall_ms = now_ms() - t0;
+    st->evals = evals;
+    st->launches = L.nlaunches;
+    st->ops = (double)evals * (double)p->ops_per_eval;
+  }
+  return 0;
+}
+
+/* The tile mg_search_lexmin cuts a range of this program into. */
+int mg_search_lexmin_tile(mg_ctx* h, mg_prog* hp, uint64_t count, uint64_t tile, uint64_t* out) {
+  if (!h || !hp || !out) return fail(MG_E_ARG, "null argument");
+  const u64 id = hid(hp);
+  CallG call;
+  if (const char* why = mw::enter(g_reg, hid(h), &id, 1, call))
+    return fail(MG_E_ARG, std::string("mg_search_lexmin_tile: ") + why);
+  *out = lexmin_plan(call.c.get(), call.ps[0].get(), count, tile, 0).tile;
   return 0;
 }
 

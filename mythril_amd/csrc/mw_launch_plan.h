@@ -250,4 +250,68 @@ inline MinPlan plan_search_min(const ProgFacts& f, u64 count, int ncu) {
   return M;
 }
 
+// mg_search_lexmin: the range is cut into tiles; each tile is evaluated with
+// verdicts and trace rows on the engine mg_eval_generated gives the program
+// when a trace is asked for, then folded into per-block records by
+// mw_lex_fold_kernel, whose grid is the same for every tile; one block reduces
+// the records after the last tile.  The verdict and trace block of one tile
+// is reused by the next (the stream orders them).
+constexpr u64 kLexDefaultTile = 1ull << 20;           // DESIGN.md "Minimize assistance": the tile sweep
+constexpr size_t kLexScratchBudget = (size_t)64 << 20;  // bytes of verdicts and trace rows of one tile, from the
+                                                        // context's pool (its idle cache is capped at 256 MiB)
+constexpr u64 kLexMaxTiles = 1ull << 16;              // one AsmArgs record each in the launch block
+constexpr u64 kLexMaxFoldBlocks = 1024;               // and so records: the one-block reduction reads them all
+
+struct LexPlan {
+  u64 tile = 0, ntiles = 0;    // candidates per tile (a multiple of kBlock), tiles; 0 tiles: refused (too many)
+  u64 fold_gx = 1;             // blocks of every fold, and block records
+  u64 eval_gx = 1;             // blocks of a full tile's evaluation
+  Engine engine{kCompiled, kWide};
+  u32 nlds = 0;                // spill words in LDS of the evaluation
+  u32 record_words = 0;        // index (2 words), then the key
+  size_t record_bytes = 0;     // the blocks' records, then the call's
+  size_t scratch_bytes = 0;    // one tile's verdicts, then its trace rows
+  size_t spill_need = 4;       // bytes of global spill buffer
+  size_t nlaunches = 0;        // 2 per tile and the reduction
+};
+
+// The largest tile a program of n_trace_rows rows may have: a multiple of
+// kBlock whose verdicts and rows fit kLexScratchBudget and whose trace block
+// stays below 2^31 bytes (eval_asm's 32-bit trace offsets, also kept on the
+// compiled interpreter: one rule).
+inline u64 lex_max_tile(u32 n_trace_rows) {
+  const u64 by_budget = kLexScratchBudget / ((u64)(1 + n_trace_rows) * 4);
+  const u64 by_offset = ((1ull << 31) - 1) / ((u64)std::max<u32>(1, n_trace_rows) * 4);
+  return std::max<u64>(kBlock, std::min(by_budget, by_offset) / kBlock * kBlock);
+}
+
+// tile: the caller's (a multiple of kBlock, checked by the caller), 0 for the
+// default; either is cut to lex_max_tile and to the range rounded up to a chunk.
+inline LexPlan plan_search_lexmin(const ProgFacts& facts, u64 count, u64 tile, u32 key_words, u32 n_trace_rows, int ncu,
+                                  bool use_asm, u32 wide_words) {
+  LexPlan L;
+  const u64 whole = count > ~0ull - (kBlock - 1) ? ~0ull / kBlock * kBlock : (count + kBlock - 1) / kBlock * kBlock;
+  L.tile = std::min({tile ? tile : kLexDefaultTile, lex_max_tile(n_trace_rows), whole});
+  const u64 ntiles = count / L.tile + (count % L.tile ? 1 : 0);
+  L.ntiles = ntiles > kLexMaxTiles ? 0 : ntiles;
+  const u64 nchunks = L.tile / kBlock;
+  L.fold_gx = std::max<u64>(1, std::min<u64>({nchunks, (u64)ncu * 4, kLexMaxFoldBlocks}));
+  L.eval_gx = std::max<u64>(1, std::min<u64>(nchunks, (u64)ncu * 8));
+  // a trace is asked for: no specialised and no assembled kernel (eval_asm)
+  ProgFacts f = facts;
+  f.jit_ready = false;
+  f.has_assembled = false;
+  L.engine = engine_of(f, use_asm, L.tile, wide_words);
+  if (L.engine.kind == kAsm)
+    (void)asm_lds_fit(f.n_spill, f.npool, asm_budget_words(f.asm_layout, false, wide_words), &L.nlds);
+  else
+    L.nlds = std::min(f.n_spill, kLdsSpillWords);
+  L.spill_need = std::max<size_t>(4, (size_t)(f.n_spill - L.nlds) * L.eval_gx * kBlock * sizeof(u32));
+  L.record_words = 2 + key_words;
+  L.record_bytes = (size_t)(L.fold_gx + 1) * L.record_words * sizeof(u32);
+  L.scratch_bytes = (size_t)(1 + n_trace_rows) * 4 * L.tile;
+  L.nlaunches = (size_t)(2 * L.ntiles + 1);
+  return L;
+}
+
 }  // namespace mw

@@ -55,6 +55,7 @@ class Witness:
     arrays: Dict[str, Dict[int, int]] = field(default_factory=dict)
     functions: Dict[str, Dict[Tuple[int, ...], int]] = field(default_factory=dict)
     objective: Optional[int] = None                  # search_min: the objective's value at index
+    objectives: Optional[List[int]] = None           # search_lexmin: every objective's value at index, in priority order
 
 
 @dataclass
@@ -532,6 +533,26 @@ def _objective_program(q: "Query", objective: Node) -> Program:
     return p
 
 
+LEX_MAX_OBJECTIVES = 8    # include/mythril_witness.h mg_search_lexmin
+
+
+def _objectives_program(q: "Query", objectives: Sequence[Node]) -> Program:
+    """search_lexmin's program: _objective_program with every objective
+    traced (a term named twice is traced once); each one's rows are read from
+    the program's trace_map, since rows are numbered in instruction order,
+    not in the order the objectives are given."""
+    from .runtime import EngineError
+    fixed = {s.name: dataclasses.replace(s, pool=None if s.pool is None else list(s.pool))
+             for s in q.program.leaf_specs}
+    traced = list({o.id: o for o in objectives}.values())
+    p = compile_query(q.lowered.conjuncts, leaf_specs=fixed, trace=traced)
+    n = len(q.program.leaf_nodes)
+    if not _same_leaves(q, p) or not np.array_equal(p.leaves[:8 * n], q.program.leaves[:8 * n]):
+        # an EngineError, so the drop-in's handlers send the query to z3
+        raise EngineError("objective program's leaf layout differs from the search program's")
+    return p
+
+
 def _combine_chunks(values: Dict[str, int], name: str, width: int) -> int:
     if name in values:
         return values[name]
@@ -681,6 +702,51 @@ class WitnessEngine:
             w = self.materialize(q, idx, dp if same else None)
             if w is not None:
                 w.objective = value
+                self.stats["hits"] += 1
+            return w
+        finally:
+            dp.free()
+
+    def search_lexmin(self, q: Query, objectives: Sequence[Node], count: Optional[int] = None,
+                      begin: int = 0) -> Optional[Witness]:
+        """The witness of ``q`` among candidates [begin, begin+count) whose
+        ``objectives`` (1 to 8 terms of q's context, at most 256 bits each,
+        compared unsigned) are lexicographically smallest, objectives[0]
+        first, ties to the lowest index; None when no candidate satisfies.
+        One call evaluates the whole range tile by tile on the engine the
+        program searches on and keeps the running minimum on the device
+        (mg_search_lexmin).  The program is q's conjuncts with every
+        objective traced, on q.program's leaf layout; the witness is
+        materialised as ``search_min`` does it, with the objectives' values in
+        ``Witness.objectives``.
+        Raises Unsupported for more than 8 objectives or one wider than 256 bits."""
+        objectives = list(objectives)
+        if not 1 <= len(objectives) <= LEX_MAX_OBJECTIVES:
+            raise Unsupported(f"{len(objectives)} objectives: 1 to {LEX_MAX_OBJECTIVES}")
+        for o in objectives:
+            width = 1 if o.width == BOOL else o.width
+            if width > isa.MAX_WIDTH:
+                raise Unsupported(f"objective of {width} bits: at most {isa.MAX_WIDTH}")
+        p = _objectives_program(q, objectives)
+        objs = []
+        for o in objectives:
+            row, cls = p.trace_map[o.id]
+            objs.append((row, ((1 if o.width == BOOL else o.width) + 31) // 32 if cls == "W" else 1))
+        count = count or self.launch_count([q])
+        dp = self.dev.load(p)
+        try:
+            idx, values, st = self.dev.search_lexmin(dp, self.seed, begin, count, objs)
+            self.stats["searches"] += 1
+            self.stats["programs"] += 1
+            self.stats["evals"] += st["evals"]
+            self.stats["kernel_ms"] += st["kernel_ms"]
+            if idx is None:
+                return None
+            # the leaf values come from this program when its leaf table is q.program's
+            same = len(p.leaf_nodes) == len(q.program.leaf_nodes)
+            w = self.materialize(q, idx, dp if same else None)
+            if w is not None:
+                w.objectives = list(values)
                 self.stats["hits"] += 1
             return w
         finally:

@@ -59,6 +59,33 @@ def search_min(p: Program, seed: int, begin: int, n: int):
     return out.decode()
 
 
+def search_lexmin(p: Program, seed: int, begin: int, n: int, objs, chunk: int = 1 << 14):
+    """(index, [objective values]) of the witness among generated candidates
+    [begin, begin+n) whose objectives are lexicographically lowest: objs is a
+    list of (row, nrows), objective k the unsigned value of p's trace rows
+    [row, row+nrows) (least significant first), objs[0] first in priority,
+    ties to the lowest index; (None, [0, ...]) without one.  The CPU twin of
+    mg_search_lexmin, over eval_generated with Python integers."""
+    if not 1 <= len(objs) <= 8 or n <= 0 or begin + n > 1 << 64:
+        raise RuntimeError("search_lexmin: 1 to 8 objectives over a non-empty range")
+    for row, nrows in objs:
+        if not 1 <= nrows <= 8 or row < 0 or row + nrows > p.n_trace_rows:
+            raise RuntimeError("search_lexmin: an objective is 1 to 8 of the program's trace rows")
+    best = None
+    for at in range(0, n, chunk):
+        m = min(chunk, n - at)
+        v, tr = eval_generated(p, seed, begin + at, m)
+        for j in np.flatnonzero(v):
+            j = int(j)
+            key = tuple(sum(int(tr[row + k, j]) << (32 * k) for k in range(nrows)) for row, nrows in objs)
+            key += (begin + at + j,)
+            if best is None or key < best:
+                best = key
+    if best is None:
+        return None, [0] * len(objs)
+    return best[-1], list(best[:-1])
+
+
 def eval_generated(p: Program, seed: int, begin: int, n: int):
     """Verdicts and trace rows of generated candidates [begin, begin+n) (host build)."""
     d, keep = make_desc(p)

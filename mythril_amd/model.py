@@ -225,7 +225,9 @@ PINNED_CHECK_MS = int(os.environ.get("MYTHRIL_AMD_PINNED_CHECK_MS", "250"))
 MINIMIZE_HINTS = os.environ.get("MYTHRIL_AMD_MINIMIZE_HINTS", "0") == "1"
 MINIMIZE_ROUNDS = int(os.environ.get("MYTHRIL_AMD_MINIMIZE_ROUNDS", "8"))   # device descent searches
 # how the hint's bound is found: "descent" (a first witness, then MINIMIZE_ROUNDS
-# searches below it), or "device": one objective-minimising launch (mg_search_min)
+# searches below it), "device": one objective-minimising launch (mg_search_min),
+# or "lex": one search minimising the objective tuple lexicographically
+# (mg_search_lexmin), which bounds the later objectives too
 MINIMIZE_MODE = os.environ.get("MYTHRIL_AMD_MINIMIZE_MODE", "descent")
 
 
@@ -249,9 +251,17 @@ def _minimize_hint(constraints, minimize, timeout):
     ``MYTHRIL_AMD_MINIMIZE_MODE=device`` the first search and the descent are one
     objective-minimising search instead (``WitnessEngine.search_min``): the
     lowest ``obj_0`` among the witnesses of the candidates one launch draws;
-    the z3 confirmation is the same.  Later objectives get no bound (the
-    witness need not be optimal in obj_0, so its later values bound nothing in
-    the lexicographic order).  The optimum is preserved, but z3 may return a
+    the z3 confirmation is the same.  In these two modes later objectives get
+    no bound (the witness need not be optimal in obj_0, so its later values
+    alone bound nothing in the lexicographic order).  With
+    ``MYTHRIL_AMD_MINIMIZE_MODE=lex`` one search (``WitnessEngine.search_lexmin``)
+    finds the witness whose tuple ``(obj_0..obj_k)`` is lexicographically
+    lowest among the candidates, for the longest prefix of ``minimize`` (at
+    most 8) made of plain variables of the script, and the hint says
+    ``(obj_0..obj_k) <=lex (b_0..b_k)`` as k+1 constraints
+    ``Or(obj_0 <u b_0, .., obj_{j-1} <u b_{j-1}, obj_j <=u b_j)``, which the
+    lexicographic optimum satisfies; a device without ``search_lexmin`` (a
+    multi-device engine) keeps the descent.  The optimum is preserved, but z3 may return a
     different model with the same objective values, i.e. different transaction
     data in the issue report: hence opt-in.  Returns the extended constraint
     collection, or None (no witness, objective not a plain variable, engine
@@ -280,11 +290,33 @@ def _minimize_hint(constraints, minimize, timeout):
             log.warning("witness engine: z3 re-check of a minimize hint failed (%s)", e)
             return False
 
+    lex_bests = None   # mode "lex": the witness's value of every objective of the prefix
     try:
         script = z3bridge.to_ir(raws)
         from .engine import prepare
         q = prepare(script.asserts, script.ctx)
-        if MINIMIZE_MODE == "device" and hasattr(eng.dev, "search_min"):
+        if MINIMIZE_MODE == "lex" and hasattr(eng.dev, "search_lexmin"):
+            # one search over the candidates the first search would draw, reduced
+            # on the device by the objective tuple in lexicographic order
+            # (WitnessEngine.search_lexmin): the longest prefix of `minimize`
+            # whose entries are plain variables of the script, at most 8
+            from .engine import LEX_MAX_OBJECTIVES
+            byname = {n.name: n for n in _walk(script.asserts) if n.op == "var"}
+            prefix = []
+            for o in minimize[:LEX_MAX_OBJECTIVES]:
+                nm = z3bridge.var_name(o.raw)
+                if nm is None or nm not in byname:
+                    break
+                prefix.append(nm)
+            if not prefix:
+                return None
+            STATS["minimize_lex"] = STATS.get("minimize_lex", 0) + 1
+            w = eng.search_lexmin(q, [byname[nm] for nm in prefix])
+            if w is None or any(nm not in w.values for nm in prefix) or not confirmed(w):
+                return None
+            lex_bests = [w.values[nm] for nm in prefix]
+            best = lex_bests[0]
+        elif MINIMIZE_MODE == "device" and hasattr(eng.dev, "search_min"):
             # one exhaustive launch over the candidates the first search would
             # draw, reduced by obj_0 on the device (WitnessEngine.search_min):
             # the lowest obj_0 among their witnesses, where the descent below
@@ -321,13 +353,21 @@ def _minimize_hint(constraints, minimize, timeout):
     except (Unsupported, RecursionError, ValueError, KeyError, EngineError):
         return None
     from mythril.laser.smt import UGE, symbol_factory
-    bound = UGE(symbol_factory.BitVecVal(best, obj.size()), obj)
+    bounds = [UGE(symbol_factory.BitVecVal(best, obj.size()), obj)]
+    if lex_bests is not None and len(lex_bests) > 1:
+        # H_j = Or(o_0 <u b_0, .., o_{j-1} <u b_{j-1}, o_j <=u b_j); H_0 is the bound
+        # above, and the conjunction says (o_0..o_k) <=lex (b_0..b_k)
+        from mythril.laser.smt import ULT, Or
+        vals = [symbol_factory.BitVecVal(b, o.size()) for b, o in zip(lex_bests, minimize)]
+        for j in range(1, len(lex_bests)):
+            bounds.append(Or(*[ULT(minimize[i], vals[i]) for i in range(j)], UGE(vals[j], minimize[j])))
     STATS["minimize_hints"] = STATS.get("minimize_hints", 0) + 1
     if type(constraints) == tuple:
-        return constraints + (bound,)
+        return constraints + tuple(bounds)
     import copy
     ext = copy.copy(constraints)
-    ext.append(bound)
+    for bound in bounds:
+        ext.append(bound)
     return ext
 
 

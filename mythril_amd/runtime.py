@@ -65,6 +65,22 @@ class MgMinResult(ctypes.Structure):
         return int(self.index), sum(int(v) << (32 * k) for k, v in enumerate(self.value))
 
 
+class MgLexObj(ctypes.Structure):
+    """include/mythril_witness.h mg_lex_obj"""
+    _fields_ = [("row", ctypes.c_uint32), ("nrows", ctypes.c_uint32)]
+
+
+class MgLexResult(ctypes.Structure):
+    """include/mythril_witness.h mg_lex_result"""
+    _fields_ = [("index", ctypes.c_uint64), ("value", (ctypes.c_uint32 * 8) * 8)]
+
+    def decode(self, nobj: int) -> Tuple[Optional[int], List[int]]:
+        """(index or None, the first nobj objectives as integers)"""
+        if self.index == MG_NONE:
+            return None, [0] * nobj
+        return int(self.index), [sum(int(v) << (32 * k) for k, v in enumerate(self.value[j])) for j in range(nobj)]
+
+
 _P = ctypes.c_void_p
 _lib = None
 _lib_lock = threading.Lock()
@@ -89,6 +105,11 @@ SIGNATURES = {
                                      ctypes.POINTER(ctypes.c_int32)]),
     "mg_search_min": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                      ctypes.POINTER(MgMinResult), ctypes.POINTER(MgStats)]),
+    "mg_search_lexmin": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                        ctypes.POINTER(MgLexObj), ctypes.c_size_t, ctypes.c_uint64,
+                                        ctypes.POINTER(MgLexResult), ctypes.POINTER(MgStats)]),
+    "mg_search_lexmin_tile": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64,
+                                             ctypes.POINTER(ctypes.c_uint64)]),
     "mg_eval": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t, _P, _P]),
     "mg_eval_generated": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t, _P, _P]),
     "mg_witness_leaves": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, _P]),
@@ -277,6 +298,31 @@ class Device:
                                                 ctypes.byref(out), ctypes.byref(st)), "mg_search_min")
         idx, val = out.decode()
         return idx, val, st.as_dict()
+
+    def search_lexmin(self, dp: DeviceProgram, seed: int, begin: int, count: int,
+                      objs: Sequence[Tuple[int, int]], tile: int = 0) -> Tuple[Optional[int], List[int], dict]:
+        """mg_search_lexmin: (index, [objective values], stats) of the witness
+        in [begin, begin+count) whose objectives, each (row, nrows) of dp's
+        trace rows and objs[0] first in priority, are lexicographically
+        lowest, ties to the lowest index; (None, [0, ...], stats) without one.
+        tile: candidates per evaluated tile (a multiple of 256; 0: the default)."""
+        if self._reap_queue:
+            self._reap()
+        arr = (MgLexObj * max(1, len(objs)))(*[MgLexObj(r, n) for r, n in objs])
+        out = MgLexResult()
+        st = MgStats()
+        _check(self.lib, self.lib.mg_search_lexmin(self.handle, dp.handle, seed & ((1 << 64) - 1), begin, count, arr,
+                                                   len(objs), tile, ctypes.byref(out), ctypes.byref(st)),
+               "mg_search_lexmin")
+        idx, vals = out.decode(len(objs))
+        return idx, vals, st.as_dict()
+
+    def search_lexmin_tile(self, dp: DeviceProgram, count: int, tile: int = 0) -> int:
+        """The tile search_lexmin cuts `count` candidates of dp into when asked for `tile`."""
+        out = ctypes.c_uint64(0)
+        _check(self.lib, self.lib.mg_search_lexmin_tile(self.handle, dp.handle, count, tile, ctypes.byref(out)),
+               "mg_search_lexmin_tile")
+        return int(out.value)
 
     def search_begin(self, progs: Sequence[DeviceProgram], seed: int, begin: int, count: int,
                      flags: int = 0) -> None:
