@@ -114,23 +114,14 @@ __device__ __forceinline__ void leaf_value_lds(const u32* __restrict__ leaf_, lp
   }
 }
 
-template <bool POOL_LDS>
-struct SearchEnv {
-  const u32* __restrict__ leaves;
-  const u32* __restrict__ pool;
-  u64 seed;
-  u64 cand;
+// The spill area of an interpreter Env (mw_interp.h): a lane's spill words
+// [0, nlds) live in LDS as [word][lane], the rest in the global spill buffer
+// as [word][thread of the grid].
+struct SpillEnv {
+  u32 nlds;
   u32* __restrict__ spillbuf;
   u64 nthreads;
   u64 gtid;
-  __device__ void leaf(u32 idx, u32 out[8]) {
-    if (POOL_LDS)
-      leaf_value_lds(leaves + (u64)idx * MW_LEAF_WORDS, (lptr)(lds_spill + nlds * kBlock), seed, cand, out);
-    else
-      leaf_value(leaves + (u64)idx * MW_LEAF_WORDS, pool, seed, cand, out);
-  }
-  __device__ void store(u32, const u32*, int) {}
-  u32 nlds;  // spill words [0, nlds) live in LDS, the rest in the global spill buffer
   __device__ void spill(u32 off, const u32* v, int n) {
     for (int k = 0; k < n; ++k) {
       const u32 wd = off + (u32)k;   // uniform
@@ -144,11 +135,26 @@ struct SearchEnv {
       v[k] = k >= n ? 0u : wd < nlds ? lds_spill[wd * kBlock + threadIdx.x] : spillbuf[(u64)(wd - nlds) * nthreads + gtid];
     }
   }
+};
+
+template <bool POOL_LDS>
+struct SearchEnv : SpillEnv {
+  const u32* __restrict__ leaves;
+  const u32* __restrict__ pool;
+  u64 seed;
+  u64 cand;
+  __device__ void leaf(u32 idx, u32 out[8]) {
+    if (POOL_LDS)
+      leaf_value_lds(leaves + (u64)idx * MW_LEAF_WORDS, (lptr)(lds_spill + nlds * kBlock), seed, cand, out);
+    else
+      leaf_value(leaves + (u64)idx * MW_LEAF_WORDS, pool, seed, cand, out);
+  }
+  __device__ void store(u32, const u32*, int) {}
   __device__ bool none(bool alive) { return __ballot(alive) == 0ull; }
   DivCount dsteps;  // division paths this wave took (wave-uniform)
 };
 
-struct EvalEnv {
+struct EvalEnv : SpillEnv {
   const u32* __restrict__ leaves;
   const u32* __restrict__ pool;
   const u32* __restrict__ in;  // SoA rows, or null -> generated
@@ -157,9 +163,6 @@ struct EvalEnv {
   u64 idx;   // candidate position within this call
   u64 seed;
   u64 cand;  // generated candidate index
-  u32* __restrict__ spillbuf;
-  u64 nthreads;
-  u64 gtid;
   __device__ void leaf(u32 li, u32 out[8]) {
     const u32* L = leaves + (u64)li * MW_LEAF_WORDS;
     if (in) {
@@ -176,22 +179,38 @@ struct EvalEnv {
     if (trace)
       for (int k = 0; k < n; ++k) trace[((u64)row + k) * ncand + idx] = v[k];
   }
-  u32 nlds;  // spill words [0, nlds) live in LDS, the rest in the global spill buffer
-  __device__ void spill(u32 off, const u32* v, int n) {
-    for (int k = 0; k < n; ++k) {
-      const u32 wd = off + (u32)k;   // uniform
-      if (wd < nlds) lds_spill[wd * kBlock + threadIdx.x] = v[k];
-      else spillbuf[(u64)(wd - nlds) * nthreads + gtid] = v[k];
-    }
-  }
-  __device__ void fill(u32 off, u32* v, int n) {
-    for (int k = 0; k < 8; ++k) {
-      const u32 wd = off + (u32)k;
-      v[k] = k >= n ? 0u : wd < nlds ? lds_spill[wd * kBlock + threadIdx.x] : spillbuf[(u64)(wd - nlds) * nthreads + gtid];
-    }
-  }
   __device__ bool none(bool) { return false; }  // eval: never exit early
   DivCount dsteps;
+};
+
+// The program's pool copied into LDS after the nlds spill rows, once per block
+// (the launch sizes LDS for it); every thread of the block calls it.
+__device__ __forceinline__ void stage_pool(const ProgDev& P, u32 nlds) {
+  u32* dst = lds_spill + nlds * kBlock;
+  for (u32 i = threadIdx.x; i < P.npool; i += kBlock) dst[i] = P.pool[i];
+  __syncthreads();
+}
+
+// A wave's counters over the chunks of its block's loop: candidates evaluated,
+// and the division paths it took x lanes; one atomic each per wave, on flush.
+struct Tally {
+  u64 evals = 0, steps = 0, full = 0, shrt = 0, gen = 0;
+  __device__ void add(u64 nvalid, const DivCount& d) {
+    evals += nvalid;
+    steps += nvalid * d.steps;
+    full += nvalid * d.full;
+    shrt += nvalid * d.shrt;
+    gen += nvalid * d.gen;
+  }
+  __device__ void flush(u64* counter) const {
+    if ((threadIdx.x & 63u) == 0u && evals) {
+      atomicAdd((unsigned long long*)counter, (unsigned long long)evals);
+      if (steps) atomicAdd((unsigned long long*)(counter + 1), (unsigned long long)steps);
+      if (full) atomicAdd((unsigned long long*)(counter + 2), (unsigned long long)full);
+      if (shrt) atomicAdd((unsigned long long*)(counter + 3), (unsigned long long)shrt);
+      if (gen) atomicAdd((unsigned long long*)(counter + 4), (unsigned long long)gen);
+    }
+  }
 };
 
 }  // namespace
@@ -205,17 +224,13 @@ __global__ __launch_bounds__(kBlock, 2) void mw_search_kernel(const ProgDev* __r
                                                            u64* __restrict__ counter,
                                                            u32* __restrict__ spillbuf, u32 nlds) {
   const ProgDev P = progs[blockIdx.y];
-  if (POOL_LDS) {
-    u32* dst = lds_spill + nlds * kBlock;
-    for (u32 i = threadIdx.x; i < P.npool; i += kBlock) dst[i] = P.pool[i];
-    __syncthreads();
-  }
+  if (POOL_LDS) stage_pool(P, nlds);
   const u64 nchunks = (count + kBlock - 1) / kBlock;
   const u64 end = begin + count;
   const u64 nthreads = (u64)gridDim.x * gridDim.y * kBlock;
   const u64 gtid = ((u64)blockIdx.y * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
   const u32 lane = threadIdx.x & 63u;
-  u64 evals = 0, lsteps = 0, lfull = 0, lshort = 0, lgen = 0;   // division paths x lanes
+  Tally tally;
   bool reported = false;   // this wave's later chunks hold only larger indices
   u32 iter = 0;
   for (u64 ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
@@ -229,7 +244,7 @@ __global__ __launch_bounds__(kBlock, 2) void mw_search_kernel(const ProgDev* __r
     }
     const u64 cand = base + threadIdx.x;
     const bool valid = cand < end;
-    SearchEnv<POOL_LDS> env{P.leaves, P.pool, seed, cand, spillbuf, nthreads, gtid, nlds};
+    SearchEnv<POOL_LDS> env{{nlds, spillbuf, nthreads, gtid}, P.leaves, P.pool, seed, cand};
     const bool ok = mw_run(P.code, P.consts, env, valid, flags);
     const u64 hit = __ballot(ok);
     if (hit && !reported) {
@@ -238,20 +253,9 @@ __global__ __launch_bounds__(kBlock, 2) void mw_search_kernel(const ProgDev* __r
         atomicMin((unsigned long long*)&out_min[blockIdx.y], (unsigned long long)cand);
       reported = true;
     }
-    const u64 nvalid = (u64)__popcll(__ballot(valid));
-    evals += nvalid;
-    lsteps += nvalid * env.dsteps.steps;
-    lfull += nvalid * env.dsteps.full;
-    lshort += nvalid * env.dsteps.shrt;
-    lgen += nvalid * env.dsteps.gen;
+    tally.add((u64)__popcll(__ballot(valid)), env.dsteps);
   }
-  if (lane == 0 && evals) {
-    atomicAdd((unsigned long long*)counter, (unsigned long long)evals);
-    if (lsteps) atomicAdd((unsigned long long*)(counter + 1), (unsigned long long)lsteps);
-    if (lfull) atomicAdd((unsigned long long*)(counter + 2), (unsigned long long)lfull);
-    if (lshort) atomicAdd((unsigned long long*)(counter + 3), (unsigned long long)lshort);
-    if (lgen) atomicAdd((unsigned long long*)(counter + 4), (unsigned long long)lgen);
-  }
+  tally.flush(counter);
 }
 
 namespace {
@@ -332,44 +336,28 @@ __global__ __launch_bounds__(kBlock, 2) void mw_search_min_kernel(const ProgDev*
                                                                u64* __restrict__ counter,
                                                                u32* __restrict__ spillbuf, u32 nlds) {
   const ProgDev P = progs[0];
-  if (POOL_LDS) {
-    u32* dst = lds_spill + nlds * kBlock;
-    for (u32 i = threadIdx.x; i < P.npool; i += kBlock) dst[i] = P.pool[i];
-    __syncthreads();
-  }
+  if (POOL_LDS) stage_pool(P, nlds);
   const u64 nchunks = (count + kBlock - 1) / kBlock;
   const u64 end = begin + count;
   const u64 nthreads = (u64)gridDim.x * kBlock;
   const u64 gtid = (u64)blockIdx.x * kBlock + threadIdx.x;
-  const u32 lane = threadIdx.x & 63u;
-  u64 evals = 0, lsteps = 0, lfull = 0, lshort = 0, lgen = 0;   // division paths x lanes
+  Tally tally;
   u32 best[kMinLimbs];
   u64 best_index;
   min_none(best, best_index);
   for (u64 ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
     const u64 cand = begin + ch * kBlock + threadIdx.x;
     const bool valid = cand < end;
-    MinEnv<POOL_LDS> env{{P.leaves, P.pool, seed, cand, spillbuf, nthreads, gtid, nlds}, {0, 0, 0, 0, 0, 0, 0, 0}};
+    MinEnv<POOL_LDS> env{{{nlds, spillbuf, nthreads, gtid}, P.leaves, P.pool, seed, cand}, {0, 0, 0, 0, 0, 0, 0, 0}};
     const bool ok = mw_run(P.code, P.consts, env, valid, 0u);
     if (ok && min_less(env.obj, cand, best, best_index)) {
 #pragma unroll
       for (int k = 0; k < kMinLimbs; ++k) best[k] = env.obj[k];
       best_index = cand;
     }
-    const u64 nvalid = (u64)__popcll(__ballot(valid));
-    evals += nvalid;
-    lsteps += nvalid * env.dsteps.steps;
-    lfull += nvalid * env.dsteps.full;
-    lshort += nvalid * env.dsteps.shrt;
-    lgen += nvalid * env.dsteps.gen;
+    tally.add((u64)__popcll(__ballot(valid)), env.dsteps);
   }
-  if (lane == 0 && evals) {
-    atomicAdd((unsigned long long*)counter, (unsigned long long)evals);
-    if (lsteps) atomicAdd((unsigned long long*)(counter + 1), (unsigned long long)lsteps);
-    if (lfull) atomicAdd((unsigned long long*)(counter + 2), (unsigned long long)lfull);
-    if (lshort) atomicAdd((unsigned long long*)(counter + 3), (unsigned long long)lshort);
-    if (lgen) atomicAdd((unsigned long long*)(counter + 4), (unsigned long long)lgen);
-  }
+  tally.flush(counter);
   min_block_reduce(best, best_index, lds_spill);
   if (threadIdx.x == 0) min_write(records + blockIdx.x, best, best_index);
 }
@@ -527,8 +515,8 @@ __global__ __launch_bounds__(kBlock, 2) void mw_eval_kernel(ProgDev P, const u32
   for (u64 ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
     const u64 idx = ch * kBlock + threadIdx.x;
     const bool valid = idx < ncand;
-    EvalEnv env{P.leaves, P.pool, in, valid ? trace : nullptr, ncand, valid ? idx : 0,
-                seed, begin + idx, spillbuf, nthreads, gtid, nlds};
+    EvalEnv env{{nlds, spillbuf, nthreads, gtid}, P.leaves, P.pool, in, valid ? trace : nullptr, ncand,
+                valid ? idx : 0, seed, begin + idx};
     const bool ok = mw_run(P.code, P.consts, env, valid, 0u);
     if (valid) verdict[idx] = ok ? 1u : 0u;
   }
@@ -1041,6 +1029,32 @@ hipError_t stage_upload(Ctx* c, size_t nmin, const ProgDev* progs, size_t nprogs
 // pinned mirror (read them there after the stream synchronises).
 hipError_t stage_readback(Ctx* c, size_t nmin) {
   return hipMemcpyAsync(c->h_blk, c->d_blk, c->off_min + nmin * sizeof(u64), hipMemcpyDeviceToHost, c->stream);
+}
+
+// The counters of the call whose stage_readback has landed, summed over the stripes.
+void read_counters(const Ctx* c, u64 ctr[kNCounters]) {
+  const u64* stripes = (const u64*)c->h_blk;
+  for (int k = 0; k < kNCounters; ++k) ctr[k] = 0;
+  for (size_t sidx = 0; sidx <= MW_CTR_STRIPES; ++sidx)
+    for (int k = 0; k < kNCounters; ++k) ctr[k] += stripes[sidx * MW_CTR_STRIPE_WORDS + k];
+}
+
+// A finished call's mg_stats (st may be null) from its counters (ctr[0]: the
+// evaluations it reports), its events e0..e1 and its start on the host clock.
+int fill_stats(Ctx* c, mg_stats* st, const u64 ctr[kNCounters], double t0, size_t launches, double ops) {
+  if (!st) return 0;
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1));
+  st->kernel_ms = ms;
+  st->wall_ms = now_ms() - t0;
+  st->evals = ctr[0];
+  st->launches = launches;
+  st->ops = ops;
+  st->lane_div_steps = ctr[1];
+  st->lane_div_full = ctr[2];
+  st->lane_div_short = ctr[3];
+  st->lane_div_general = ctr[4];
+  return 0;
 }
 
 // One launch of an asm engine over gx blocks on the records at dprog and dargs
@@ -1727,34 +1741,41 @@ static int search_complete(Ctx* c, Pending& P, uint64_t* out_min_idx, mg_stats* 
       mw::step_times_add("mg_search", "gpu: queued program uploads", u);
   }
   c->eu_live = false;
-  const u64* stripes = (const u64*)c->h_blk;
   const u64* mins = (const u64*)(c->h_blk + c->off_min);
-  u64 ctr[kNCounters] = {0, 0, 0, 0, 0};
-  for (size_t sidx = 0; sidx <= MW_CTR_STRIPES; ++sidx)
-    for (int k = 0; k < kNCounters; ++k) ctr[k] += stripes[sidx * MW_CTR_STRIPE_WORDS + k];
+  u64 ctr[kNCounters];
+  read_counters(c, ctr);   // evals: summed over every program's blocks
   // specialised launches under MW_FLAG_NO_COUNT counted nothing: every
   // candidate of the range was evaluated (no stop-after-hit)
-  const u64 evals = ctr[0] + ((P.flags & MW_FLAG_NO_COUNT) ? P.count * P.plan.special.size() : 0u);
+  if (P.flags & MW_FLAG_NO_COUNT) ctr[0] += P.count * P.plan.special.size();
   for (size_t i = 0; i < P.ps.size(); ++i) out_min_idx[i] = mins[P.plan.slot[i]];
-  if (st) {
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1));
-    st->kernel_ms = ms;
-    st->wall_ms = now_ms() - P.t0;
-    st->evals = evals;  // summed over every program's blocks
-    st->launches = P.plan.nlaunches;
-    st->ops = (double)evals / (double)P.ps.size() * (double)P.plan.ops;
-    st->lane_div_steps = ctr[1];
-    st->lane_div_full = ctr[2];
-    st->lane_div_short = ctr[3];
-    st->lane_div_general = ctr[4];
-  }
+  return fill_stats(c, st, ctr, P.t0, P.plan.nlaunches, (double)ctr[0] / (double)P.ps.size() * (double)P.plan.ops);
+}
+
+// Between mg_search_begin and mg_search_end every call that launches work on the context is refused.
+static int pending_refusal(const char* name) {
+  return fail(MG_E_ARG, std::string(name) + ": a search begun with mg_search_begin is pending");
+}
+
+// A call's entry on context h and its programs ids[0..n): handles resolved,
+// reference-held and locked for the whole call (mw_handles.h), on a context
+// with no search pending (while_pending: a call that launches nothing).
+static int call_enter(mw::Registry<Ctx, Prog>& reg, const char* name, mg_ctx* h, const u64* ids, size_t n, CallG& call,
+                      bool while_pending = false) {
+  if (const char* why = mw::enter(reg, hid(h), ids, n, call)) return fail(MG_E_ARG, std::string(name) + ": " + why);
+  if (call.c->pending.active && !while_pending) return pending_refusal(name);
   return 0;
 }
 
+// ... of a call on one program
+static int prog_enter(mw::Registry<Ctx, Prog>& reg, const char* name, mg_ctx* h, const mg_prog* hp, CallG& call,
+                      bool while_pending = false) {
+  if (!h || !hp) return fail(MG_E_ARG, "null argument");
+  const u64 id = hid(hp);
+  return call_enter(reg, name, h, &id, 1, call, while_pending);
+}
+
 // What mg_search and mg_search_begin share: the argument checks, the flags as
-// the kernels get them, and the call's entry (handles resolved, reference-held
-// and locked for the whole call, mw_handles.h) on a context with no search pending.
+// the kernels get them, and the call's entry.
 static int search_enter(mw::Registry<Ctx, Prog>& reg, const char* name, mg_ctx* h, mg_prog* const* hprogs, size_t nprog,
                         uint64_t begin, uint64_t count, uint32_t* flags, mw::CallMark& mark, CallG& call) {
   if (!h || !hprogs || nprog == 0) return fail(MG_E_ARG, "null argument");
@@ -1764,10 +1785,7 @@ static int search_enter(mw::Registry<Ctx, Prog>& reg, const char* name, mg_ctx* 
   std::vector<u64> ids(nprog);
   for (size_t i = 0; i < nprog; ++i) ids[i] = hid(hprogs[i]);
   mark.step("lock", nprog);
-  if (const char* why = mw::enter(reg, hid(h), ids.data(), nprog, call))
-    return fail(MG_E_ARG, std::string(name) + ": " + why);
-  if (call.c->pending.active) return fail(MG_E_ARG, std::string(name) + ": a search begun with mg_search_begin is pending");
-  return 0;
+  return call_enter(reg, name, h, ids.data(), nprog, call);
 }
 
 int mg_search(mg_ctx* h, mg_prog* const* hprogs, size_t nprog, uint64_t seed, uint64_t begin,
@@ -1802,6 +1820,27 @@ int mg_search_begin(mg_ctx* h, mg_prog* const* hprogs, size_t nprog, uint64_t se
   return 0;
 }
 
+// What mg_search_min and mg_search_lexmin do around their plan and enqueue
+// (the context's mu held).  Before: the call's start on the host clock, the
+// device, a clean error state (launch errors are read back after the enqueue).
+static int reduce_begin(Ctx* c, mw::CallMark& mark, double* t0) {
+  mark.step("plan");
+  *t0 = now_ms();
+  HIPCHK(hipSetDevice(c->dev));
+  (void)hipGetLastError();
+  return 0;
+}
+
+// After: the call's one synchronisation; its pool buffers need not wait again.
+static int reduce_finish(Ctx* c, mw::CallMark& mark, u64 count, std::initializer_list<Scratch*> bufs) {
+  mark.step("sync", count);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (Scratch* s : bufs) s->synced = true;
+  c->uploads_landed();   // the stream drained: a queued program upload has landed
+  c->eu_live = false;
+  return 0;
+}
+
 // Plan and enqueue mg_search_min's launches (the context's mu held): the
 // launch records upload (zeroed counters, the program's record), the min
 // kernel, the records' reduction, and the readbacks of the counters and of the
@@ -1833,51 +1872,30 @@ static int search_min_enqueue(Ctx* c, const Prog* p, uint64_t seed, uint64_t beg
 
 int mg_search_min(mg_ctx* h, mg_prog* hp, uint64_t seed, uint64_t begin, uint64_t count, mg_min_result* out,
                   mg_stats* st) {
-  if (!h || !hp || !out) return fail(MG_E_ARG, "null argument");
+  if (!out) return fail(MG_E_ARG, "null argument");
   if (count == 0 || begin + count < begin) return fail(MG_E_ARG, "bad candidate range");
-  const u64 id = hid(hp);
   mw::CallMark mark("mg_search_min");
   mark.step("lock", count);
   CallG call;
-  if (const char* why = mw::enter(g_reg, hid(h), &id, 1, call)) return fail(MG_E_ARG, std::string("mg_search_min: ") + why);
-  if (call.c->pending.active) return fail(MG_E_ARG, "mg_search_min: a search begun with mg_search_begin is pending");
+  int rc = prog_enter(g_reg, "mg_search_min", h, hp, call);
+  if (rc) return rc;
   Ctx* c = call.c.get();
   const Prog* p = call.ps[0].get();
   if (p->desc.n_trace_rows == 0 || p->desc.n_trace_rows > (u32)kMinLimbs)
     return fail(MG_E_ARG, "mg_search_min: the objective is the program's trace rows: 1 to 8 of them");
-  mark.step("plan");
-  const double t0 = now_ms();
-  HIPCHK(hipSetDevice(c->dev));
-  (void)hipGetLastError();  // start from a clean error state: launch errors are read back below
+  double t0;
+  rc = reduce_begin(c, mark, &t0);
+  if (rc) return rc;
   const MinPlan M = plan_search_min(facts_of(p), count, c->ncu);
   mark.step("enqueue", count);
   Scratch rec(c, M.record_bytes);
-  int rc = search_min_enqueue(c, p, seed, begin, count, M, rec);
+  rc = search_min_enqueue(c, p, seed, begin, count, M, rec);
+  if (rc == 0) rc = reduce_finish(c, mark, count, {&rec});
   if (rc) return rc;   // (rec waits for the stream before its buffer goes back to the pool)
-  mark.step("sync", count);
-  HIPCHK(hipStreamSynchronize(c->stream));
-  rec.synced = true;
-  c->uploads_landed();   // the stream drained: a queued program upload has landed
-  c->eu_live = false;
   std::memcpy(out, c->h_rb, sizeof(MinRecord));
-  if (st) {
-    const u64* stripes = (const u64*)c->h_blk;
-    u64 ctr[kNCounters] = {0, 0, 0, 0, 0};
-    for (size_t sidx = 0; sidx <= MW_CTR_STRIPES; ++sidx)
-      for (int k = 0; k < kNCounters; ++k) ctr[k] += stripes[sidx * MW_CTR_STRIPE_WORDS + k];
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1));
-    st->kernel_ms = ms;
-    st->wall_ms = now_ms() - t0;
-    st->evals = ctr[0];
-    st->launches = 2;
-    st->ops = (double)ctr[0] * (double)p->ops_per_eval;
-    st->lane_div_steps = ctr[1];
-    st->lane_div_full = ctr[2];
-    st->lane_div_short = ctr[3];
-    st->lane_div_general = ctr[4];
-  }
-  return 0;
+  u64 ctr[kNCounters];
+  read_counters(c, ctr);
+  return fill_stats(c, st, ctr, t0, 2, (double)ctr[0] * (double)p->ops_per_eval);
 }
 
 // The witness evaluations of mg_search_end: each witness program is uploaded,
@@ -1938,7 +1956,7 @@ static int witness_enqueue(Ctx* c, const std::shared_ptr<Ctx>& cref, Pending& P,
     const Prog* wp = W.wps[k].get();
     (void)asm_lds_fit(wp->dev.n_spill, wp->dev.npool, asm_budget_words(wp->asm_layout, false, wide_lds_words()),
                       &wnlds[k]);
-    spill = std::max(spill, (size_t)(wp->dev.n_spill - wnlds[k]) * kBlock * sizeof(u32));
+    spill = std::max(spill, spill_bytes(wp->dev.n_spill, wnlds[k], 1));
   }
   int rc = ensure_spill(c, spill);   // (a regrow frees the old buffer: hipFree waits for the search)
   if (rc) return rc;
@@ -2060,11 +2078,8 @@ static int eval_common(Ctx* c, const Prog* p, const uint32_t* leaves_soa, size_t
   if (!verdict || ncand == 0) return fail(MG_E_ARG, "null argument");
   HIPCHK(hipSetDevice(c->dev));
   (void)hipGetLastError();  // clean error state before the launch below
-  const u64 nchunks = (ncand + kBlock - 1) / kBlock;
-  const u64 gx = std::min<u64>(nchunks, (u64)c->ncu * 8);
-  const u64 nthreads = gx * kBlock;
-  const u32 nlds = std::min(p->dev.n_spill, kLdsSpillWords);
-  int rc = ensure_spill(c, std::max<size_t>(4, (size_t)(p->dev.n_spill - nlds) * nthreads * sizeof(u32)));
+  const EvalPlan E = plan_eval(p->dev.n_spill, std::min(p->dev.n_spill, kLdsSpillWords), ncand, c->ncu);
+  int rc = ensure_spill(c, E.spill_need);
   if (rc) return rc;
   const size_t nin = leaves_soa ? (size_t)p->desc.n_input_rows * ncand : 0;
   const size_t ntr = trace ? (size_t)p->desc.n_trace_rows * ncand : 0;
@@ -2076,7 +2091,7 @@ static int eval_common(Ctx* c, const Prog* p, const uint32_t* leaves_soa, size_t
   if (nin && hipMemcpyAsync(d_in, leaves_soa, nin * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess)
     return fail(MG_E_HIP, "eval input copy");
   if (ntr && !p->trace_full) hipMemsetAsync(d_t, 0, tb, c->stream);
-  const hipError_t e = eval_readback(c, launch_eval_compiled(c, p, d_in, ncand, seed, begin, d_v, d_t, gx, nlds),
+  const hipError_t e = eval_readback(c, launch_eval_compiled(c, p, d_in, ncand, seed, begin, d_v, d_t, E.gx, E.nlds),
                                      "eval/sync", d_v, vb, tb, verdict, trace);
   s_in.synced = s_vt.synced = e == hipSuccess;
   if (e != hipSuccess) return fail(MG_E_HIP, std::string("eval: ") + hipGetErrorString(e));
@@ -2085,13 +2100,10 @@ static int eval_common(Ctx* c, const Prog* p, const uint32_t* leaves_soa, size_t
 
 int mg_eval(mg_ctx* h, const mg_prog* hp, const uint32_t* leaves_soa, size_t ncand, uint32_t* verdict,
             uint32_t* trace) {
-  if (!h || !hp) return fail(MG_E_ARG, "null argument");
-  const u64 id = hid(hp);
   mw::CallMark mark("mg_eval");
   mark.step("lock", ncand);
   CallG call;
-  if (const char* why = mw::enter(g_reg, hid(h), &id, 1, call)) return fail(MG_E_ARG, std::string("mg_eval: ") + why);
-  if (call.c->pending.active) return fail(MG_E_ARG, "a search begun with mg_search_begin is pending on this context");
+  if (int rc = prog_enter(g_reg, "mg_eval", h, hp, call)) return rc;
   mark.step("eval", ncand);
   const Prog* p = call.ps[0].get();
   if (p->desc.nleaves && p->desc.n_input_rows && !leaves_soa) return fail(MG_E_ARG, "leaves_soa required");
@@ -2124,20 +2136,19 @@ static int eval_asm(Ctx* c, const Prog* p, uint64_t seed, uint64_t begin, size_t
   (void)hipGetLastError();
   int rc = ensure_launch(c, 1, 1);
   if (rc) return rc;
-  const u64 nchunks = (count + kBlock - 1) / kBlock;
-  const u64 gx = std::min<u64>(nchunks, (u64)c->ncu * 8);
-  rc = ensure_spill(c, std::max<size_t>(4, (size_t)(p->dev.n_spill - nlds) * gx * kBlock * sizeof(u32)));
+  const EvalPlan E = plan_eval(f.n_spill, nlds, count, c->ncu);
+  rc = ensure_spill(c, E.spill_need);
   if (rc) return rc;
   // verdicts and trace rows in one device block: one readback
   const size_t vb = count * 4, tb = ntr * 4;
   Scratch s_v(c, vb + tb);
   if (!s_v.p) return fail(MG_E_NOMEM, "eval verdict alloc");
   u32 *d_v = s_v.u(), *d_t = ntr ? d_v + count : nullptr;
-  const AsmArgs aa = eval_asm_args(c, seed, begin, count, gx, nlds, d_v, d_t);
+  const AsmArgs aa = eval_asm_args(c, seed, begin, count, E.gx, nlds, d_v, d_t);
   hipError_t e = ntr && !p->trace_full ? hipMemsetAsync(d_t, 0, tb, c->stream) : hipSuccess;
   if (e == hipSuccess) e = stage_upload(c, 1, assembled ? &p->dev : &p->adev, 1, &aa, 1);
   if (e == hipSuccess) {
-    rc = launch_eval_asm(c, p, assembled, c->d_asmargs, gx, nlds);
+    rc = launch_eval_asm(c, p, assembled, c->d_asmargs, E.gx, nlds);
     if (rc) return rc;
   }
   e = eval_readback(c, e, "eval_asm/sync", d_v, vb, tb, verdict, trace);
@@ -2150,14 +2161,10 @@ static int eval_asm(Ctx* c, const Prog* p, uint64_t seed, uint64_t begin, size_t
 
 int mg_eval_generated(mg_ctx* h, const mg_prog* hp, uint64_t seed, uint64_t begin, size_t count,
                       uint32_t* verdict, uint32_t* trace) {
-  if (!h || !hp) return fail(MG_E_ARG, "null argument");
-  const u64 id = hid(hp);
   mw::CallMark mark("mg_eval_generated");
   mark.step("lock", count);
   CallG call;
-  if (const char* why = mw::enter(g_reg, hid(h), &id, 1, call))
-    return fail(MG_E_ARG, std::string("mg_eval_generated: ") + why);
-  if (call.c->pending.active) return fail(MG_E_ARG, "a search begun with mg_search_begin is pending on this context");
+  if (int rc = prog_enter(g_reg, "mg_eval_generated", h, hp, call)) return rc;
   mark.step("eval", count);
   Ctx* c = call.c.get();
   const Prog* p = call.ps[0].get();
@@ -2250,16 +2257,15 @@ static int search_lexmin_enqueue(Ctx* c, const Prog* p, uint64_t seed, uint64_t 
 int mg_search_lexmin(mg_ctx* h, mg_prog* hp, uint64_t seed, uint64_t begin, uint64_t count, const mg_lex_obj* objs,
                      size_t nobj, uint64_t tile, mg_lex_result* out, mg_stats* st) {
   static_assert(sizeof(mg_lex_obj) == sizeof(LexObj), "mg_lex_obj is a LexObj");
-  if (!h || !hp || !out || !objs) return fail(MG_E_ARG, "null argument");
+  if (!out || !objs) return fail(MG_E_ARG, "null argument");
   if (count == 0 || begin + count < begin) return fail(MG_E_ARG, "bad candidate range");
   if (nobj == 0 || nobj > (size_t)kLexMaxObj) return fail(MG_E_ARG, "mg_search_lexmin: 1 to 8 objectives");
   if (tile % kBlock) return fail(MG_E_ARG, "mg_search_lexmin: the tile is a multiple of 256 candidates (0: the default)");
-  const u64 id = hid(hp);
   mw::CallMark mark("mg_search_lexmin");
   mark.step("lock", count);
   CallG call;
-  if (const char* why = mw::enter(g_reg, hid(h), &id, 1, call)) return fail(MG_E_ARG, std::string("mg_search_lexmin: ") + why);
-  if (call.c->pending.active) return fail(MG_E_ARG, "mg_search_lexmin: a search begun with mg_search_begin is pending");
+  int rc = prog_enter(g_reg, "mg_search_lexmin", h, hp, call);
+  if (rc) return rc;
   Ctx* c = call.c.get();
   const Prog* p = call.ps[0].get();
   LexObj key[kLexMaxObj];
@@ -2269,21 +2275,16 @@ int mg_search_lexmin(mg_ctx* h, mg_prog* hp, uint64_t seed, uint64_t begin, uint
         key[k].nrows > p->desc.n_trace_rows - key[k].row)
       return fail(MG_E_ARG, "mg_search_lexmin: an objective is 1 to 8 of the program's trace rows");
   }
-  mark.step("plan");
-  const double t0 = now_ms();
-  HIPCHK(hipSetDevice(c->dev));
-  (void)hipGetLastError();  // start from a clean error state: launch errors are read back below
+  double t0;
+  rc = reduce_begin(c, mark, &t0);
+  if (rc) return rc;
   const LexPlan L = lexmin_plan(c, p, count, tile, lex_key_words(key, (u32)nobj));
   if (!L.ntiles) return fail(MG_E_ARG, "mg_search_lexmin: more than 65536 tiles: a larger tile or a shorter range");
   mark.step("enqueue", count);
   Scratch vt(c, L.scratch_bytes), rec(c, L.record_bytes);
-  int rc = search_lexmin_enqueue(c, p, seed, begin, count, key, (u32)nobj, L, vt, rec);
+  rc = search_lexmin_enqueue(c, p, seed, begin, count, key, (u32)nobj, L, vt, rec);
+  if (rc == 0) rc = reduce_finish(c, mark, count, {&vt, &rec});
   if (rc) return rc;   // (the buffers wait for the stream before they go back to the pool)
-  mark.step("sync", count);
-  HIPCHK(hipStreamSynchronize(c->stream));
-  vt.synced = rec.synced = true;
-  c->uploads_landed();   // the stream drained: a queued program upload has landed
-  c->eu_live = false;
   const u32* r = (const u32*)c->h_rb;
   std::memset(out, 0, sizeof(*out));
   out->index = lex_record_index(r);
@@ -2292,31 +2293,19 @@ int mg_search_lexmin(mg_ctx* h, mg_prog* hp, uint64_t seed, uint64_t begin, uint
     for (size_t k = 0; k < nobj; kw += key[k].nrows, ++k)
       for (u32 l = 0; l < key[k].nrows; ++l) out->value[k][l] = kw[l];
   }
-  if (st) {
-    const u64* stripes = (const u64*)c->h_blk;
-    u64 evals = 0;
-    for (size_t sidx = 0; sidx <= MW_CTR_STRIPES; ++sidx) evals += stripes[sidx * MW_CTR_STRIPE_WORDS];
-    // (mw_eval_kernel counts nothing: it evaluates every candidate it is given)
-    if (L.engine.kind != kAsm) evals = count;
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1));
-    std::memset(st, 0, sizeof(*st));
-    st->kernel_ms = ms;
-    st->wall_ms = now_ms() - t0;
-    st->evals = evals;
-    st->launches = L.nlaunches;
-    st->ops = (double)evals * (double)p->ops_per_eval;
-  }
-  return 0;
+  u64 ctr[kNCounters];
+  read_counters(c, ctr);
+  // the evaluations alone, no division counts (mw_eval_kernel counts nothing:
+  // it evaluates every candidate it is given)
+  const u64 lex[kNCounters] = {L.engine.kind == kAsm ? ctr[0] : count, 0, 0, 0, 0};
+  return fill_stats(c, st, lex, t0, L.nlaunches, (double)lex[0] * (double)p->ops_per_eval);
 }
 
 /* The tile mg_search_lexmin cuts a range of this program into. */
 int mg_search_lexmin_tile(mg_ctx* h, mg_prog* hp, uint64_t count, uint64_t tile, uint64_t* out) {
-  if (!h || !hp || !out) return fail(MG_E_ARG, "null argument");
-  const u64 id = hid(hp);
+  if (!out) return fail(MG_E_ARG, "null argument");
   CallG call;
-  if (const char* why = mw::enter(g_reg, hid(h), &id, 1, call))
-    return fail(MG_E_ARG, std::string("mg_search_lexmin_tile: ") + why);
+  if (int rc = prog_enter(g_reg, "mg_search_lexmin_tile", h, hp, call, true)) return rc;   // plans only
   *out = lexmin_plan(call.c.get(), call.ps[0].get(), count, tile, 0).tile;
   return 0;
 }
@@ -2339,7 +2328,7 @@ int mg_eval_program(mg_ctx* h, const mg_prog_desc* d, uint64_t seed, uint64_t be
   mark.step("lock");
   std::lock_guard<std::mutex> lk(c->mu);
   if (c->dead) return fail(MG_E_ARG, "mg_eval_program: the context was freed during the call");
-  if (c->pending.active) return fail(MG_E_ARG, "a search begun with mg_search_begin is pending on this context");
+  if (c->pending.active) return pending_refusal("mg_eval_program");
   HIPCHK(hipSetDevice(c->dev));
   std::shared_ptr<Prog> p;
   rc = load_locked(cref, d, p);
@@ -2355,14 +2344,11 @@ int mg_eval_program(mg_ctx* h, const mg_prog_desc* d, uint64_t seed, uint64_t be
 }
 
 int mg_witness_leaves(mg_ctx* h, const mg_prog* hp, uint64_t seed, uint64_t index, uint32_t* out) {
-  if (!h || !hp || !out) return fail(MG_E_ARG, "null argument");
-  const u64 id = hid(hp);
+  if (!out) return fail(MG_E_ARG, "null argument");
   mw::CallMark mark("mg_witness_leaves");
   mark.step("lock");
   CallG call;
-  if (const char* why = mw::enter(g_reg, hid(h), &id, 1, call))
-    return fail(MG_E_ARG, std::string("mg_witness_leaves: ") + why);
-  if (call.c->pending.active) return fail(MG_E_ARG, "a search begun with mg_search_begin is pending on this context");
+  if (int rc = prog_enter(g_reg, "mg_witness_leaves", h, hp, call)) return rc;
   mark.step("launch + sync");
   Ctx* c = call.c.get();
   const Prog* p = call.ps[0].get();
@@ -2386,11 +2372,10 @@ int mg_witness_leaves(mg_ctx* h, const mg_prog* hp, uint64_t seed, uint64_t inde
 int mg_valu_peak(mg_ctx* h, uint32_t mul, double* ops_per_s, double* kernel_ms) {
   if (!h || !ops_per_s) return fail(MG_E_ARG, "null argument");
   CallG call;
-  if (const char* why = mw::enter(g_reg, hid(h), nullptr, 0, call)) return fail(MG_E_ARG, std::string("mg_valu_peak: ") + why);
-  if (call.c->pending.active) return fail(MG_E_ARG, "a search begun with mg_search_begin is pending on this context");
+  if (int rc = call_enter(g_reg, "mg_valu_peak", h, nullptr, 0, call)) return rc;
   Ctx* c = call.c.get();
   HIPCHK(hipSetDevice(c->dev));
-  const u32 blocks = (u32)c->ncu * 8, iters = 4096;
+  const u32 waves_per_simd = 8, blocks = (u32)c->ncu * waves_per_simd, iters = 4096;   // (a block: a wave per SIMD)
   u32* d = nullptr;
   HIPCHK(hipMalloc(&d, (size_t)blocks * kBlock * 4));
   hipLaunchKernelGGL(mw_valu_peak_kernel, dim3(blocks), dim3(kBlock), 0, c->stream, d, 16u, mul);  // warm
@@ -2412,8 +2397,7 @@ int mg_keccak256_device(mg_ctx* h, const uint8_t* d_data, const uint64_t* d_off,
   mw::CallMark mark("mg_keccak256_device");
   mark.step("lock", n);
   CallG call;
-  if (const char* why = mw::enter(g_reg, hid(h), nullptr, 0, call)) return fail(MG_E_ARG, std::string("mg_keccak256: ") + why);
-  if (call.c->pending.active) return fail(MG_E_ARG, "a search begun with mg_search_begin is pending on this context");
+  if (int rc = call_enter(g_reg, "mg_keccak256", h, nullptr, 0, call)) return rc;
   Ctx* c = call.c.get();
   HIPCHK(hipSetDevice(c->dev));
   const double t0 = now_ms();

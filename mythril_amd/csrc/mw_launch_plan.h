@@ -75,6 +75,29 @@ inline Args asm_args(u64 seed, u64 begin, u64 count, u32 flags, u64 gx, u32 nlds
   return a;
 }
 
+// Bytes of global spill buffer of a one-program launch of gx blocks: the spill
+// words past the nlds in LDS, one u32 per thread each (never an empty buffer).
+inline size_t spill_bytes(u32 n_spill, u32 nlds, u64 gx) {
+  return std::max<size_t>(4, (size_t)(n_spill - nlds) * gx * kBlock * sizeof(u32));
+}
+
+// One program over `count` candidates with the whole chip to itself (an
+// evaluation on mw_eval_kernel or an asm engine, a search on an assembled
+// kernel): enough blocks to fill the chip several times over, at most one per
+// chunk.  nlds is the caller's: kLdsSpillWords at most on the compiled
+// interpreter, asm_lds_fit's on an asm engine.
+struct EvalPlan {
+  u64 gx;              // blocks
+  u32 nlds;            // spill words in LDS
+  size_t spill_need;   // bytes of global spill buffer
+};
+
+inline EvalPlan plan_eval(u32 n_spill, u32 nlds, u64 count, int ncu) {
+  const u64 nchunks = (count + kBlock - 1) / kBlock;
+  const u64 gx = std::max<u64>(1, std::min<u64>(nchunks, (u64)ncu * 8));
+  return {gx, nlds, spill_bytes(n_spill, nlds, gx)};
+}
+
 // What the plan needs to know of a loaded program.
 struct ProgFacts {
   u32 n_spill = 0, npool = 0, n_insn = 0;
@@ -203,12 +226,12 @@ inline SearchPlan plan_search(const ProgFacts* facts, size_t n, u64 count, int n
     ++S.nlaunches;
   }
   // assembled kernels: one program, the whole chip each
-  const u64 agx = std::min<u64>((u64)ncu * 8, nchunks);
   for (size_t i : gasb) {
     u32 nlds = 0;
     (void)asm_lds_fit(facts[i].n_spill, facts[i].npool, asm_budget_words(kWide, true, wide_words), &nlds);
-    S.assembled.push_back({agx, nlds});
-    S.spill_need = std::max(S.spill_need, (size_t)(facts[i].n_spill - nlds) * agx * kBlock * sizeof(u32));
+    const EvalPlan A = plan_eval(facts[i].n_spill, nlds, count, ncu);
+    S.assembled.push_back({A.gx, nlds});
+    S.spill_need = std::max(S.spill_need, A.spill_need);
   }
   S.nlaunches += gasb.size() + S.special.size();
   return S;
@@ -245,7 +268,7 @@ inline MinPlan plan_search_min(const ProgFacts& f, u64 count, int ncu) {
   M.pool_lds = f.npool && asm_lds_bytes(M.nlds, f.npool) <= (size_t)kLdsSpillWords * kBlock * 4;
 #endif
   M.lds_bytes = std::max(asm_lds_bytes(M.nlds, M.pool_lds ? f.npool : 0), kMinReduceBytes);
-  M.spill_need = std::max<size_t>(4, (size_t)(f.n_spill - M.nlds) * M.gx * kBlock * sizeof(u32));
+  M.spill_need = spill_bytes(f.n_spill, M.nlds, M.gx);
   M.record_bytes = (size_t)(M.gx + 1) * kMinRecordBytes;
   return M;
 }
@@ -294,9 +317,7 @@ inline LexPlan plan_search_lexmin(const ProgFacts& facts, u64 count, u64 tile, u
   L.tile = std::min({tile ? tile : kLexDefaultTile, lex_max_tile(n_trace_rows), whole});
   const u64 ntiles = count / L.tile + (count % L.tile ? 1 : 0);
   L.ntiles = ntiles > kLexMaxTiles ? 0 : ntiles;
-  const u64 nchunks = L.tile / kBlock;
-  L.fold_gx = std::max<u64>(1, std::min<u64>({nchunks, (u64)ncu * 4, kLexMaxFoldBlocks}));
-  L.eval_gx = std::max<u64>(1, std::min<u64>(nchunks, (u64)ncu * 8));
+  L.fold_gx = std::max<u64>(1, std::min<u64>({L.tile / kBlock, (u64)ncu * 4, kLexMaxFoldBlocks}));
   // a trace is asked for: no specialised and no assembled kernel (eval_asm)
   ProgFacts f = facts;
   f.jit_ready = false;
@@ -306,7 +327,9 @@ inline LexPlan plan_search_lexmin(const ProgFacts& facts, u64 count, u64 tile, u
     (void)asm_lds_fit(f.n_spill, f.npool, asm_budget_words(f.asm_layout, false, wide_words), &L.nlds);
   else
     L.nlds = std::min(f.n_spill, kLdsSpillWords);
-  L.spill_need = std::max<size_t>(4, (size_t)(f.n_spill - L.nlds) * L.eval_gx * kBlock * sizeof(u32));
+  const EvalPlan E = plan_eval(f.n_spill, L.nlds, L.tile, ncu);
+  L.eval_gx = E.gx;
+  L.spill_need = E.spill_need;
   L.record_words = 2 + key_words;
   L.record_bytes = (size_t)(L.fold_gx + 1) * L.record_words * sizeof(u32);
   L.scratch_bytes = (size_t)(1 + n_trace_rows) * 4 * L.tile;

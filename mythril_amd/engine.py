@@ -516,31 +516,22 @@ def _witness_program(prog: Program, traced: List[Node]) -> Program:
     return compile_query([], leaf_specs=fixed, trace=traced)
 
 
-def _objective_program(q: "Query", objective: Node) -> Program:
-    """search_min's program: q's conjuncts with `objective` traced (a narrow
-    one through STORE_N, one row; a wide one through STORE_W, eight), on
-    q.program's leaf layout as _witness_program keeps it (the pool fields
-    already assigned), so that candidate i is the assignment q.program
-    checks at i."""
-    from .runtime import EngineError
-    fixed = {s.name: dataclasses.replace(s, pool=None if s.pool is None else list(s.pool))
-             for s in q.program.leaf_specs}
-    p = compile_query(q.lowered.conjuncts, leaf_specs=fixed, trace=[objective])
-    n = len(q.program.leaf_nodes)
-    if not _same_leaves(q, p) or not np.array_equal(p.leaves[:8 * n], q.program.leaves[:8 * n]):
-        # an EngineError, so the drop-in's handlers send the query to z3
-        raise EngineError("objective program's leaf layout differs from the search program's")
-    return p
-
-
 LEX_MAX_OBJECTIVES = 8    # include/mythril_witness.h mg_search_lexmin
 
 
+def _objective_width(o: Node) -> int:
+    return 1 if o.width == BOOL else o.width
+
+
 def _objectives_program(q: "Query", objectives: Sequence[Node]) -> Program:
-    """search_lexmin's program: _objective_program with every objective
-    traced (a term named twice is traced once); each one's rows are read from
-    the program's trace_map, since rows are numbered in instruction order,
-    not in the order the objectives are given."""
+    """search_min's and search_lexmin's program: q's conjuncts with every
+    objective traced (a narrow one through STORE_N, one row; a wide one
+    through STORE_W, eight; a term named twice is traced once), on q.program's
+    leaf layout as _witness_program keeps it (the pool fields already
+    assigned), so that candidate i is the assignment q.program checks at i.
+    Each objective's rows are read from the program's trace_map, since rows
+    are numbered in instruction order, not in the order the objectives are
+    given."""
     from .runtime import EngineError
     fixed = {s.name: dataclasses.replace(s, pool=None if s.pool is None else list(s.pool))
              for s in q.program.leaf_specs}
@@ -683,29 +674,8 @@ class WitnessEngine:
         not re-evaluated here (the drop-in re-checks it with z3).  To
         maximise a term t, pass ``bvnot(t)``: the smallest complement is the
         largest t.  Raises Unsupported for an objective wider than 256 bits."""
-        width = 1 if objective.width == BOOL else objective.width
-        if width > isa.MAX_WIDTH:
-            raise Unsupported(f"objective of {width} bits: at most {isa.MAX_WIDTH}")
-        p = _objective_program(q, objective)
-        count = count or self.launch_count([q])
-        dp = self.dev.load(p)
-        try:
-            idx, value, st = self.dev.search_min(dp, self.seed, begin, count)
-            self.stats["searches"] += 1
-            self.stats["programs"] += 1
-            self.stats["evals"] += st["evals"]
-            self.stats["kernel_ms"] += st["kernel_ms"]
-            if idx is None:
-                return None
-            # the leaf values come from this program when its leaf table is q.program's
-            same = len(p.leaf_nodes) == len(q.program.leaf_nodes)
-            w = self.materialize(q, idx, dp if same else None)
-            if w is not None:
-                w.objective = value
-                self.stats["hits"] += 1
-            return w
-        finally:
-            dp.free()
+        return self._search_reduced(q, [objective], count, "objective",
+                                    lambda dp, p, n: self.dev.search_min(dp, self.seed, begin, n))
 
     def search_lexmin(self, q: Query, objectives: Sequence[Node], count: Optional[int] = None,
                       begin: int = 0) -> Optional[Witness]:
@@ -723,19 +693,29 @@ class WitnessEngine:
         objectives = list(objectives)
         if not 1 <= len(objectives) <= LEX_MAX_OBJECTIVES:
             raise Unsupported(f"{len(objectives)} objectives: 1 to {LEX_MAX_OBJECTIVES}")
+
+        def run(dp, p, n):
+            objs = []
+            for o in objectives:
+                row, cls = p.trace_map[o.id]
+                objs.append((row, (_objective_width(o) + 31) // 32 if cls == "W" else 1))
+            idx, values, st = self.dev.search_lexmin(dp, self.seed, begin, n, objs)
+            return idx, list(values), st
+        return self._search_reduced(q, objectives, count, "objectives", run)
+
+    def _search_reduced(self, q: Query, objectives: Sequence[Node], count: Optional[int], field: str,
+                        run) -> Optional[Witness]:
+        """What search_min and search_lexmin share: the objectives' program
+        loaded, ``run(dp, program, count)`` -> (index, value, stats) on it, the
+        witness materialised at the index with the value in its ``field``."""
         for o in objectives:
-            width = 1 if o.width == BOOL else o.width
-            if width > isa.MAX_WIDTH:
-                raise Unsupported(f"objective of {width} bits: at most {isa.MAX_WIDTH}")
+            if _objective_width(o) > isa.MAX_WIDTH:
+                raise Unsupported(f"objective of {_objective_width(o)} bits: at most {isa.MAX_WIDTH}")
         p = _objectives_program(q, objectives)
-        objs = []
-        for o in objectives:
-            row, cls = p.trace_map[o.id]
-            objs.append((row, ((1 if o.width == BOOL else o.width) + 31) // 32 if cls == "W" else 1))
         count = count or self.launch_count([q])
         dp = self.dev.load(p)
         try:
-            idx, values, st = self.dev.search_lexmin(dp, self.seed, begin, count, objs)
+            idx, value, st = run(dp, p, count)
             self.stats["searches"] += 1
             self.stats["programs"] += 1
             self.stats["evals"] += st["evals"]
@@ -746,7 +726,7 @@ class WitnessEngine:
             same = len(p.leaf_nodes) == len(q.program.leaf_nodes)
             w = self.materialize(q, idx, dp if same else None)
             if w is not None:
-                w.objectives = list(values)
+                setattr(w, field, value)
                 self.stats["hits"] += 1
             return w
         finally:

@@ -166,6 +166,27 @@ int main() {
     const Rec r = asm_args<Rec>(9, 0, 1, 0, 1, 12, 0, nullptr);
     CHECK(r.end == 1 && r.gstride == 1024 && r.nchunks == 1 && r.gdx == 1 && r.nprog == 0 && r.nlds == 12);
   }
+  {  // an evaluation: min(chunks, 2048) blocks, the spill words past nlds x the grid's threads x 4 bytes
+    EvalPlan E = plan_eval(0, 0, 1, ncu);
+    CHECK(E.gx == 1 && E.nlds == 0 && E.spill_need == 4);   // one lane; never an empty spill buffer
+    E = plan_eval(0, 0, 257, ncu);
+    CHECK(E.gx == 2);                                       // a ragged second chunk
+    E = plan_eval(0, 0, 524288, ncu);
+    CHECK(E.gx == 2048);                                    // 256 * 2048 candidates: a block per chunk still
+    E = plan_eval(0, 0, 524289, ncu);
+    CHECK(E.gx == 2048);                                    // one more: the cap, blocks stride the chunks
+    E = plan_eval(80, 80, M, ncu);
+    CHECK(E.gx == 2048 && E.nlds == 80 && E.spill_need == 4);   // kLdsSpillWords words: all in LDS
+    E = plan_eval(83, 80, M, ncu);
+    CHECK(E.nlds == 80 && E.spill_need == 6291456);         // 3 words x 2048 blocks x 256 threads x 4 bytes
+    E = plan_eval(83, 80, 257, ncu);
+    CHECK(E.gx == 2 && E.spill_need == 6144);               // 3 x 2 x 256 x 4
+    E = plan_eval(100, 78, M, ncu);                         // an asm engine's split (the first case's pool)
+    CHECK(E.nlds == 78 && E.spill_need == 46137344);        // 22 x 2048 x 256 x 4
+    E = plan_eval(5, 5, M, 4);
+    CHECK(E.gx == 32 && E.spill_need == 4);                 // a 4-CU device
+    CHECK(spill_bytes(12, 10, 1) == 2048 && spill_bytes(7, 7, 1) == 4);   // a one-block witness evaluation
+  }
   if (failures) return std::printf("%d checks failed\n", failures), 1;
   std::puts("OK");
   return 0;

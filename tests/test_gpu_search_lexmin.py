@@ -15,7 +15,7 @@ import pytest
 from mythril_amd.compiler import compile_program
 from mythril_amd.engine import WitnessEngine, prepare
 from mythril_amd.ir import Ctx
-from mythril_amd.runtime import MG_NONE, MgLexObj, MgLexResult, MgStats
+from mythril_amd.runtime import MG_NONE, MgLexObj, MgLexResult, MgMinResult, MgStats
 from oracle import cdag
 from tests import lexmatrix, minmatrix
 from tests.helpers import oracle_models
@@ -145,6 +145,31 @@ def test_single_objective_agrees_with_search_min(dev):
                     assert (lidx, lvals[0]) == (idx, val) == minmatrix.expected(case.name, begin, n), (case.name, begin, n)
         finally:
             dp.free()
+
+
+def test_one_objective_on_the_division_program_agrees_with_search_min(dev):
+    """The divide-and-remainder program of tests/test_gpu_search_min.py
+    test_counters_count_every_candidate over one lane, a ragged range across
+    chunks and more chunks than a block's first pass: mg_search_min and
+    mg_search_lexmin with the one objective {row 0, n_trace_rows} return the
+    same index and limbs, and each reports every candidate and its launches."""
+    c = Ctx()
+    a, b = c.var("a", 256), c.var("b", 256)
+    p = compile_program([c.app("bvugt", c.app("bvudiv", a, b), c.const(3, 256))], trace=[c.app("bvurem", a, b)])
+    dp = dev.load(p)
+    try:
+        for begin, n in ((0, 1), (7, 1000), (0, 4096 + 37)):
+            mout, mst = MgMinResult(), MgStats()
+            assert dev.lib.mg_search_min(dev.handle, dp.handle, SEED, begin, n, ctypes.byref(mout), ctypes.byref(mst)) == 0
+            rc, lidx, lvalue, lst = _raw(dev, dp, begin, n, [(0, p.n_trace_rows)])
+            assert rc == 0 and lidx == int(mout.index), (begin, n)
+            assert lvalue[0] == [int(x) for x in mout.value] and not any(any(row) for row in lvalue[1:]), (begin, n)
+            used = dev.search_lexmin_tile(dp, n, 0)
+            tiles = (n + used - 1) // used
+            assert mst.evals == n and lst.evals == n, (begin, n, mst.evals, lst.evals)
+            assert mst.launches == 2 and lst.launches == 2 * tiles + 1, (begin, n, mst.launches, lst.launches)
+    finally:
+        dp.free()
 
 
 def test_refusals(dev):

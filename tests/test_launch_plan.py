@@ -35,11 +35,13 @@ def test_the_library_plans_through_the_header():
     k = (CSRC / "mw_kernels.hip").read_text()
     assert "#include <hip" not in plan and '#include "mw_' not in plan     # host-only, stands alone
     assert '#include "mw_launch_plan.h"' in k
-    for name in ("engine_of(", "plan_search(", "asm_args<AsmArgs>(", "asm_lds_bytes("):
+    for name in ("engine_of(", "plan_search(", "asm_args<AsmArgs>(", "asm_lds_bytes(", "plan_eval("):
         assert name in k, name
-    for defined_once in ("inline bool asm_lds_fit(", "inline Engine engine_of(", "inline SearchPlan plan_search("):
+    for defined_once in ("inline bool asm_lds_fit(", "inline Engine engine_of(", "inline SearchPlan plan_search(",
+                         "inline EvalPlan plan_eval("):
         assert plan.count(defined_once) == 1, defined_once
-    # no second fit and no record formula left in the library
+    # no second fit, no record formula and no evaluation grid or spill size left in the library
     assert "bool asm_lds_fit(" not in k and "gstride" not in k
+    assert "ncu * 8" not in k and "n_spill - " not in k
     from mythril_amd import build
     assert "mw_launch_plan.h" in build.HEADERS and "mw_inflight.h" in build.HEADERS

@@ -167,6 +167,24 @@ def test_default_mode_call_sequence_is_unchanged(hinting):
     assert _is_uge(ext[-1].raw.node, X, ext[-1].raw.node.args[0].val) and x0 <= ext[-1].raw.node.args[0].val
 
 
+def test_search_min_is_search_lexmin_of_one_objective(hinting, monkeypatch):
+    """Both searches compile through one function: search_min(q, o) and
+    search_lexmin(q, [o]) load the same program and return the same witness."""
+    loaded = []
+    load = hinting.dev.load
+    monkeypatch.setattr(hinting.dev, "load", lambda p: (loaded.append(p), load(p))[1])
+    q = prepare(CONS, CTX)
+    a = hinting.eng.search_min(q, X, count=1024)
+    b = hinting.eng.search_lexmin(q, [X], count=1024)
+    assert [c[:3] for c in hinting.dev.calls] == [("search_min", 0, 1024), ("search_lexmin", 0, 1024)]
+    pa, pb = loaded
+    for field in ("code", "consts", "leaves", "pool"):
+        assert np.array_equal(getattr(pa, field), getattr(pb, field)), field
+    assert a is not None and b is not None and a.index == b.index
+    assert a.objective == b.objectives[0] == a.values["lxx"] and b.objectives == [a.objective]
+    assert all(eval_nodes(CONS, a.values)[c.id] for c in CONS)
+
+
 def test_engine_search_lexmin(hinting):
     q = prepare(CONS, CTX)
     want, _, n = _range_lexmin(hinting.eng, ("lxy", "lxx"))
