@@ -177,6 +177,41 @@ int mg_search_lexmin(mg_ctx* ctx, mg_prog* prog, uint64_t seed, uint64_t begin, 
  * reference: a diagnostic for tests and benchmarks. */
 int mg_search_lexmin_tile(mg_ctx* ctx, mg_prog* prog, uint64_t count, uint64_t tile, uint64_t* out);
 
+typedef struct {
+  uint64_t satisfied;      /* candidates failing no row */
+  uint64_t near_index;     /* MG_NONE never: count >= 1 */
+  uint32_t near_nfail;     /* rows the nearest candidate fails (0: it is a witness) */
+  uint32_t reserved;
+} mg_blame_result;
+/* Why a search missed: per-conjunct failure counts over candidates
+ * [begin, begin+count).  The program's trace rows [row, row + nrows), 1..1024
+ * of them, each hold one conjunct's truth for a candidate: a row that reads 0
+ * is a failed conjunct, any other value a satisfied one.  With F(c) the set of
+ * rows candidate c fails: out_fail[j] counts the candidates with j in F(c),
+ * out_sole[j] those with F(c) = {j} (rejected by that conjunct alone),
+ * out->satisfied those with F(c) empty, and out->near_index / near_nfail are
+ * the candidate of lowest (|F(c)|, index).  All counts are exact and depend on
+ * neither grid, tile nor engine.  The program's own verdict is ignored (every
+ * row of every candidate is stored whatever it is) and so are the rows outside
+ * [row, row + nrows).  The range is cut into tiles by mg_search_lexmin's rule
+ * (mg_search_lexmin_tile answers for both calls), each tile is evaluated with
+ * its trace rows on the engine mg_eval_generated uses when a trace is asked
+ * for (no attached kernel), then folded into the call's totals on the device
+ * with atomic adds, without a reduction kernel: stats->launches == 2 * tiles,
+ * stats->evals == count, one upload and one synchronisation.  Refused with
+ * MG_E_ARG for a null output, count == 0 or a wrapping range, nrows of 0 or
+ * above 1024, rows outside the program's trace, a tile that is no multiple of
+ * 256, more than 65536 tiles, and while a search begun with mg_search_begin is
+ * pending.  Same handle, lock and in-flight protocol as mg_search_lexmin.
+ * Replaces nothing in the reference: for a set without a model z3's
+ * Optimize.check answers unsat or unknown
+ * (mythril/laser/smt/solver/solver.py:50-66) and names no conjunct.  A
+ * diagnostic for misses (WitnessEngine.explain_miss). */
+int mg_search_blame(mg_ctx* ctx, mg_prog* prog, uint64_t seed, uint64_t begin, uint64_t count,
+                    uint32_t row, uint32_t nrows, uint64_t tile,
+                    uint64_t* out_fail, uint64_t* out_sole,   /* nrows each */
+                    mg_blame_result* out, mg_stats* stats);
+
 /* Evaluate one program on explicit assignments: leaves_soa has n_input_rows
  * rows of ncand u32 (row r, candidate i at [r*ncand + i]).  verdict[i] = 0/1;
  * trace (may be NULL) receives n_trace_rows rows of ncand u32. */

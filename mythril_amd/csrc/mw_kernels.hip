@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -30,6 +31,7 @@
 #include "../../include/mythril_witness.h"
 #include "mw_asm_abi.h"
 #include "mw_asm_interp.inc"
+#include "mw_blame.h"
 #include "mw_handles.h"
 #include "mw_inflight.h"
 #include "mw_interp.h"
@@ -460,6 +462,60 @@ __global__ __launch_bounds__(kBlock) void mw_lex_reduce_kernel(const u32* __rest
       for (u32 k = 0; k < record_words; ++k) out[k] = src[k];
     }
   }
+}
+
+// mg_search_blame's tile fold: the n candidates of one evaluated tile (row r of
+// tile offset j at trace[r * stride + j]; candidate begin + base + j) counted
+// into the call's totals (mw_blame.h: fail[nrows], sole[nrows], satisfied, the
+// nearest key; u64 words).  Rows [row, row + nrows) each hold one conjunct's
+// truth: 0 is a failed conjunct.  A thread walks its candidate's rows (loads
+// coalesced across the wave) and keeps two registers, its count of failed rows
+// and the last of them (blame_step); per row the wave ballots "my row is 0"
+// and lane 0 adds the popcount to the block's LDS bin, so a row nobody fails
+// costs no atomic.  A lane with one failure adds to sole[last], the lanes with
+// none are balloted into `satisfied`.  The chunk loop is uniform over the
+// block: every lane reaches every ballot, and a lane at or past n is false in
+// all of them.  The block then flushes its non-zero bins with 64-bit atomic
+// adds and its lowest key with one atomicMin (ties: the lowest offset), so the
+// totals depend on neither grid nor tile.  A block folds at most one tile
+// (2^23 candidates at most, mw_launch_plan.h): its u32 bins cannot overflow.
+__global__ __launch_bounds__(kBlock) void mw_blame_fold_kernel(const u32* __restrict__ trace, u64 stride, u32 n,
+                                                                u64 base, u32 row, u32 nrows,
+                                                                unsigned long long* __restrict__ totals) {
+  __shared__ u32 bins[2 * kBlameMaxRows + 1];
+  __shared__ u64 red[kBlock / 64];
+  const u32 nbins = blame_bins(nrows);
+  u32 *fail = bins, *sole = bins + nrows, *satisfied = bins + 2 * nrows;
+  for (u32 i = threadIdx.x; i < nbins; i += kBlock) bins[i] = 0u;
+  __syncthreads();
+  const bool lane0 = (threadIdx.x & 63u) == 0u;
+  u64 best = kBlameNoKey;
+  for (u64 j0 = (u64)blockIdx.x * kBlock; j0 < n; j0 += (u64)gridDim.x * kBlock) {
+    const u64 j = j0 + threadIdx.x;
+    const bool live = j < n;
+    BlameWalk w;
+#pragma unroll 4
+    for (u32 r = 0; r < nrows; ++r) {
+      const u32 v = live ? trace[(u64)(row + r) * stride + j] : 1u;
+      blame_step(w, r, v);
+      const u64 failed = __ballot(live && v == 0u);
+      if (failed != 0ull && lane0) atomicAdd(&fail[r], (u32)__popcll(failed));
+    }
+    if (live && w.nfail == 1u) atomicAdd(&sole[w.last], 1u);
+    const u64 none = __ballot(live && w.nfail == 0u);
+    if (none != 0ull && lane0) atomicAdd(satisfied, (u32)__popcll(none));
+    if (live) best = blame_nearer(best, blame_key(w.nfail, base + j));
+  }
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) best = blame_nearer(best, (u64)__shfl_xor((unsigned long long)best, m));
+  if (lane0) red[threadIdx.x >> 6] = best;
+  __syncthreads();   // the waves' keys, and every add to the bins
+  if (threadIdx.x == 0) {
+    for (u32 k = 1; k < kBlock / 64; ++k) best = blame_nearer(best, red[k]);
+    if (best != kBlameNoKey) atomicMin(&totals[nbins], (unsigned long long)best);
+  }
+  for (u32 i = threadIdx.x; i < nbins; i += kBlock)
+    if (bins[i]) atomicAdd(&totals[i], (unsigned long long)bins[i]);
 }
 
 // Threaded-dispatch interpreter (mythril_amd/asmgen.py -> mw_asm_interp.inc):
@@ -2199,37 +2255,39 @@ static LexPlan lexmin_plan(const Ctx* c, const Prog* p, u64 count, u64 tile, u32
                             wide_lds_words());
 }
 
-// Enqueue mg_search_lexmin's work (the context's mu held).  Every buffer is
-// sized first: spill, the launch block (one AsmArgs record per tile on the asm
-// interpreter, and one more record's room that carries the objectives), the
-// tile's verdict and trace block (vt) and the records (rec) from the pool.
-// Then, on the stream: one upload, the records set to MG_NONE, per tile the
-// evaluation and the fold, the reduction, the readbacks.  Between the first
-// launch and the caller's synchronisation nothing allocates, frees or waits.
-static int search_lexmin_enqueue(Ctx* c, const Prog* p, uint64_t seed, uint64_t begin, uint64_t count,
-                                 const LexObj* objs, u32 nobj, const LexPlan& L, Scratch& vt, Scratch& rec) {
-  static_assert(sizeof(AsmArgs) >= kLexMaxObj * sizeof(LexObj), "the objectives travel in one AsmArgs record's room");
+// The tiles of mg_search_lexmin and mg_search_blame (the context's mu held):
+// the launch block and the spill buffer sized (one AsmArgs record per tile on
+// the asm interpreter, then `extra`'s n_extra records, which land at
+// c->d_asmargs + tile_records(L)), the call's one upload, init() for the memsets
+// of the call's result buffers, then per tile the evaluation of its verdicts
+// and trace rows into vt (reused: the stream orders the tiles) and
+// fold(n, tile_begin, d_v, d_t), which launches the tile's fold.  The caller has
+// sized every other buffer before: between the first launch and the caller's
+// synchronisation nothing allocates, frees or waits.
+static size_t tile_records(const LexPlan& L) { return L.engine.kind == kAsm ? (size_t)L.ntiles : 0; }
+
+typedef std::function<hipError_t()> TileInit;
+typedef std::function<void(u64 n, u64 tile_begin, const u32* d_v, const u32* d_t)> TileFold;
+
+static int tiles_enqueue(Ctx* c, const Prog* p, uint64_t seed, uint64_t begin, uint64_t count, const LexPlan& L,
+                         Scratch& vt, const AsmArgs* extra, size_t n_extra, const TileInit& init,
+                         const TileFold& fold) {
   const bool on_asm = L.engine.kind == kAsm;
-  const size_t ntile_args = on_asm ? (size_t)L.ntiles : 0;
-  int rc = ensure_launch(c, 1, ntile_args + 1);
+  const size_t ntile_args = tile_records(L);
+  int rc = ensure_launch(c, 1, ntile_args + n_extra);
   if (rc) return rc;
   rc = ensure_spill(c, L.spill_need);
   if (rc) return rc;
-  if (!vt.p || !rec.p) return fail(MG_E_NOMEM, "mg_search_lexmin: tile and record buffers");
-  const size_t rec_bytes = (size_t)L.record_words * sizeof(u32);
-  if (!ensure_readback(c, rec_bytes)) return fail(MG_E_NOMEM, "mg_search_lexmin: readback buffer");
-  u32 *d_v = vt.u(), *d_t = d_v + L.tile, *d_rec = rec.u();
+  u32 *d_v = vt.u(), *d_t = d_v + L.tile;
   const u32 nrows = p->desc.n_trace_rows;
   auto tile_n = [&](u64 t) { return std::min<u64>(L.tile, count - t * L.tile); };
   auto tile_gx = [&](u64 n) { return std::min<u64>((n + kBlock - 1) / kBlock, L.eval_gx); };
-  std::vector<AsmArgs> ha(ntile_args + 1);
+  std::vector<AsmArgs> ha(ntile_args + n_extra);
   for (size_t t = 0; t < ntile_args; ++t)
     ha[t] = eval_asm_args(c, seed, begin + t * L.tile, tile_n(t), tile_gx(tile_n(t)), L.nlds, d_v, d_t);
-  std::memset(&ha[ntile_args], 0, sizeof(AsmArgs));
-  std::memcpy(&ha[ntile_args], objs, nobj * sizeof(LexObj));
-  const LexObj* d_objs = (const LexObj*)(c->d_asmargs + ntile_args);
+  for (size_t k = 0; k < n_extra; ++k) ha[ntile_args + k] = extra[k];
   HIPCHK(stage_upload(c, 1, on_asm ? &p->adev : &p->dev, 1, ha.data(), ha.size()));
-  HIPCHK(hipMemsetAsync(d_rec, 0xff, L.record_bytes, c->stream));   // every record at MG_NONE
+  HIPCHK(init());
   HIPCHK(hipEventRecord(c->e0, c->stream));
   for (u64 t = 0; t < L.ntiles; ++t) {
     const u64 n = tile_n(t), tb = begin + t * L.tile;
@@ -2240,13 +2298,41 @@ static int search_lexmin_enqueue(Ctx* c, const Prog* p, uint64_t seed, uint64_t 
     } else {
       HIPCHK(launch_eval_compiled(c, p, nullptr, n, seed, tb, d_v, d_t, tile_gx(n), L.nlds));
     }
-    hipLaunchKernelGGL(mw_lex_fold_kernel, dim3((u32)L.fold_gx), dim3(kBlock), 0, c->stream, (const u32*)d_v,
-                       (const u32*)d_t, n, (u32)n, tb, d_objs, nobj, d_rec, L.record_words);
+    fold(n, tb, (const u32*)d_v, (const u32*)d_t);
     HIPCHK(hipGetLastError());
   }
+  return 0;
+}
+
+// Enqueue mg_search_lexmin's work (the context's mu held).  Every buffer is
+// sized first: the tile's verdict and trace block (vt) and the records (rec)
+// from the pool, the readback buffer, and in tiles_enqueue the spill buffer
+// and the launch block, with one more record's room that carries the
+// objectives.  Then, on the stream: one upload, the records set to MG_NONE,
+// per tile the evaluation and the fold, the reduction, the readbacks.
+static int search_lexmin_enqueue(Ctx* c, const Prog* p, uint64_t seed, uint64_t begin, uint64_t count,
+                                 const LexObj* objs, u32 nobj, const LexPlan& L, Scratch& vt, Scratch& rec) {
+  static_assert(sizeof(AsmArgs) >= kLexMaxObj * sizeof(LexObj), "the objectives travel in one AsmArgs record's room");
+  if (!vt.p || !rec.p) return fail(MG_E_NOMEM, "mg_search_lexmin: tile and record buffers");
+  const size_t rec_bytes = (size_t)L.record_words * sizeof(u32);
+  if (!ensure_readback(c, rec_bytes)) return fail(MG_E_NOMEM, "mg_search_lexmin: readback buffer");
+  u32* d_rec = rec.u();
+  AsmArgs key;
+  std::memset(&key, 0, sizeof(AsmArgs));
+  std::memcpy(&key, objs, nobj * sizeof(LexObj));
+  // (read by the folds only after tiles_enqueue has sized the launch block)
+  auto d_objs = [&] { return (const LexObj*)(c->d_asmargs + tile_records(L)); };
+  int rc = tiles_enqueue(
+      c, p, seed, begin, count, L, vt, &key, 1,
+      [&] { return hipMemsetAsync(d_rec, 0xff, L.record_bytes, c->stream); },   // every record at MG_NONE
+      [&](u64 n, u64 tb, const u32* d_v, const u32* d_t) {
+        hipLaunchKernelGGL(mw_lex_fold_kernel, dim3((u32)L.fold_gx), dim3(kBlock), 0, c->stream, d_v, d_t, n, (u32)n, tb,
+                           d_objs(), nobj, d_rec, L.record_words);
+      });
+  if (rc) return rc;
   u32* d_out = d_rec + L.fold_gx * L.record_words;
   hipLaunchKernelGGL(mw_lex_reduce_kernel, dim3(1), dim3(kBlock), 0, c->stream, (const u32*)d_rec, (u32)L.fold_gx,
-                     d_objs, nobj, L.record_words, d_out);
+                     d_objs(), nobj, L.record_words, d_out);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(c->e1, c->stream));
   HIPCHK(stage_readback(c, 1));   // the counters
@@ -2308,6 +2394,75 @@ int mg_search_lexmin_tile(mg_ctx* h, mg_prog* hp, uint64_t count, uint64_t tile,
   if (int rc = prog_enter(g_reg, "mg_search_lexmin_tile", h, hp, call, true)) return rc;   // plans only
   *out = lexmin_plan(call.c.get(), call.ps[0].get(), count, tile, 0).tile;
   return 0;
+}
+
+// Enqueue mg_search_blame's work (the context's mu held): the totals (tot, from
+// the pool) zeroed and their nearest key set to all ones, then tiles_enqueue
+// with mw_blame_fold_kernel as every tile's fold, the readbacks.
+static int search_blame_enqueue(Ctx* c, const Prog* p, uint64_t seed, uint64_t begin, uint64_t count, u32 row,
+                                u32 nrows, const BlamePlan& B, Scratch& vt, Scratch& tot) {
+  const LexPlan& L = B.tiles;
+  if (!vt.p || !tot.p) return fail(MG_E_NOMEM, "mg_search_blame: tile and total buffers");
+  if (!ensure_readback(c, B.total_bytes)) return fail(MG_E_NOMEM, "mg_search_blame: readback buffer");
+  unsigned long long* d_tot = (unsigned long long*)tot.p;
+  const size_t count_bytes = (size_t)blame_bins(nrows) * sizeof(u64);
+  int rc = tiles_enqueue(
+      c, p, seed, begin, count, L, vt, nullptr, 0,
+      [&] {
+        const hipError_t e = hipMemsetAsync(d_tot, 0, count_bytes, c->stream);
+        return e != hipSuccess ? e : hipMemsetAsync(d_tot + blame_bins(nrows), 0xff, sizeof(u64), c->stream);
+      },
+      [&](u64 n, u64 tb, const u32*, const u32* d_t) {
+        hipLaunchKernelGGL(mw_blame_fold_kernel, dim3((u32)L.fold_gx), dim3(kBlock), 0, c->stream, d_t, n, (u32)n,
+                           tb - begin, row, nrows, d_tot);
+      });
+  if (rc) return rc;
+  HIPCHK(hipEventRecord(c->e1, c->stream));
+  HIPCHK(stage_readback(c, 1));   // the counters
+  HIPCHK(hipMemcpyAsync(c->h_rb, d_tot, B.total_bytes, hipMemcpyDeviceToHost, c->stream));
+  return 0;
+}
+
+int mg_search_blame(mg_ctx* h, mg_prog* hp, uint64_t seed, uint64_t begin, uint64_t count, uint32_t row,
+                    uint32_t nrows, uint64_t tile, uint64_t* out_fail, uint64_t* out_sole, mg_blame_result* out,
+                    mg_stats* st) {
+  if (!out || !out_fail || !out_sole) return fail(MG_E_ARG, "null argument");
+  if (count == 0 || begin + count < begin) return fail(MG_E_ARG, "bad candidate range");
+  if (nrows == 0 || nrows > kBlameMaxRows) return fail(MG_E_ARG, "mg_search_blame: 1 to 1024 conjunct rows");
+  if (tile % kBlock) return fail(MG_E_ARG, "mg_search_blame: the tile is a multiple of 256 candidates (0: the default)");
+  mw::CallMark mark("mg_search_blame");
+  mark.step("lock", count);
+  CallG call;
+  int rc = prog_enter(g_reg, "mg_search_blame", h, hp, call);
+  if (rc) return rc;
+  Ctx* c = call.c.get();
+  const Prog* p = call.ps[0].get();
+  if (row >= p->desc.n_trace_rows || nrows > p->desc.n_trace_rows - row)
+    return fail(MG_E_ARG, "mg_search_blame: the conjunct rows are rows of the program's trace");
+  double t0;
+  rc = reduce_begin(c, mark, &t0);
+  if (rc) return rc;
+  const BlamePlan B = plan_search_blame(facts_of(p), count, tile, nrows, p->desc.n_trace_rows, c->ncu, asm_enabled(),
+                                        wide_lds_words());
+  if (!B.tiles.ntiles) return fail(MG_E_ARG, "mg_search_blame: more than 65536 tiles: a larger tile or a shorter range");
+  mark.step("enqueue", count);
+  Scratch vt(c, B.tiles.scratch_bytes), tot(c, B.total_bytes);
+  rc = search_blame_enqueue(c, p, seed, begin, count, row, nrows, B, vt, tot);
+  if (rc == 0) rc = reduce_finish(c, mark, count, {&vt, &tot});
+  if (rc) return rc;   // (the buffers wait for the stream before they go back to the pool)
+  const u64* t = (const u64*)c->h_rb;
+  std::memcpy(out_fail, t, (size_t)nrows * sizeof(u64));
+  std::memcpy(out_sole, t + nrows, (size_t)nrows * sizeof(u64));
+  const u64 key = t[blame_bins(nrows)];   // count >= 1: some block has written it
+  std::memset(out, 0, sizeof(*out));
+  out->satisfied = t[2 * nrows];
+  out->near_index = begin + blame_key_offset(key);
+  out->near_nfail = blame_key_nfail(key);
+  u64 ctr[kNCounters];
+  read_counters(c, ctr);
+  // the evaluations alone, as mg_search_lexmin reports them
+  const u64 ev[kNCounters] = {B.tiles.engine.kind == kAsm ? ctr[0] : count, 0, 0, 0, 0};
+  return fill_stats(c, st, ev, t0, B.nlaunches, (double)ev[0] * (double)p->ops_per_eval);
 }
 
 // One-shot evaluation of a program that is not kept (a witness program:

@@ -337,4 +337,28 @@ inline LexPlan plan_search_lexmin(const ProgFacts& facts, u64 count, u64 tile, u
   return L;
 }
 
+// mg_search_blame: plan_search_lexmin's tiles, engine and fold grid (so
+// mg_search_lexmin_tile answers for both calls), each tile folded by
+// mw_blame_fold_kernel into the call's totals with atomic adds: no block
+// records and no reduction kernel, 2 launches per tile.  A tile has at most
+// lex_max_tile(1) = 2^23 candidates (a block's u32 bins cannot overflow) and a
+// call at most kLexMaxTiles of them: an offset from `begin` stays below 2^48,
+// the low field of mw_blame.h's key.
+static_assert(kLexScratchBudget / 8 * kLexMaxTiles < (1ull << 48), "a candidate's offset fits the blame key");
+
+struct BlamePlan {
+  LexPlan tiles;             // tile, ntiles (0: refused), fold_gx, engine, eval_gx, nlds, scratch_bytes, spill_need
+  size_t total_bytes = 0;    // u64 words: fail[nrows], sole[nrows], satisfied, the nearest key
+  size_t nlaunches = 0;      // 2 per tile
+};
+
+inline BlamePlan plan_search_blame(const ProgFacts& facts, u64 count, u64 tile, u32 nrows, u32 n_trace_rows, int ncu,
+                                   bool use_asm, u32 wide_words) {
+  BlamePlan B;
+  B.tiles = plan_search_lexmin(facts, count, tile, 0, n_trace_rows, ncu, use_asm, wide_words);
+  B.total_bytes = (size_t)(2 * (u64)nrows + 2) * sizeof(u64);
+  B.nlaunches = (size_t)(2 * B.tiles.ntiles);
+  return B;
+}
+
 }  // namespace mw

@@ -544,6 +544,69 @@ def _objectives_program(q: "Query", objectives: Sequence[Node]) -> Program:
     return p
 
 
+BLAME_MAX_ROWS = 1024     # include/mythril_witness.h mg_search_blame (csrc/mw_blame.h kBlameMaxRows)
+CONGRUENCE = -1           # MissProfile: the congruence conjuncts' one bin, where conjunct numbers are listed
+
+
+@dataclass
+class MissProfile:
+    """WitnessEngine.explain_miss: why ``count`` candidates of a query held no
+    witness (or how many did).  A conjunct number j is q.conjuncts[j]:
+    lower_constraints rewrites each input conjunct into exactly one lowered
+    conjunct, in order, and appends the congruence conjuncts after them.  The
+    congruence conjuncts share one bin (``CONGRUENCE`` where numbers are
+    listed)."""
+    count: int
+    satisfied: int                    # candidates that fail nothing
+    fail: List[int]                   # fail[j]: candidates that fail conjunct j
+    sole: List[int]                   # sole[j]: candidates that fail conjunct j and nothing else
+    congruence_fail: Optional[int]    # the same for the conjunction of the congruence conjuncts;
+    congruence_sole: Optional[int]    # None when the query has none
+    nearest: Optional[Witness]        # the candidate that fails the fewest, ties to the lowest index
+    nearest_nfail: int                # how many bins it fails (0: it is a witness)
+    nearest_failed: List[int]         # which
+    stats: dict = field(default_factory=dict)
+
+    def blocking(self) -> List[int]:
+        """Conjunct numbers by ``sole`` descending, then ``fail`` descending
+        (then the number): the conjuncts that alone reject the most
+        candidates first."""
+        bins = [(s, f, j) for j, (s, f) in enumerate(zip(self.sole, self.fail))]
+        if self.congruence_fail is not None:
+            bins.append((self.congruence_sole, self.congruence_fail, CONGRUENCE))
+        return [j for _, _, j in sorted(bins, key=lambda b: (-b[0], -b[1], b[2] if b[2] >= 0 else len(bins)))]
+
+
+def _profile_program(q: "Query") -> Tuple[Program, List[int], Optional[int]]:
+    """explain_miss's program: nothing to check, one Bool traced per main
+    lowered conjunct (q.lowered.conjuncts without its last
+    q.lowered.congruence entries; STORE_N, one row each) and one more for the
+    conjunction of the congruence conjuncts, on q.program's leaf layout as
+    _objectives_program keeps it.  Returns the program, each main conjunct's
+    trace row and the congruence's (or None).  Rows are read from trace_map:
+    they are numbered in instruction order, and a conjunct that occurs twice is
+    one term and one row."""
+    from .runtime import EngineError
+    low = q.lowered
+    nmain = len(low.conjuncts) - low.congruence
+    main, cong = low.conjuncts[:nmain], low.conjuncts[nmain:]
+    all_cong = None
+    if cong:
+        all_cong = cong[0] if len(cong) == 1 else q.ctx.app("and", *cong)
+    traced = list({t.id: t for t in main + ([all_cong] if cong else [])}.values())
+    if len(traced) > BLAME_MAX_ROWS:
+        raise Unsupported(f"{len(traced)} conjunct rows: at most {BLAME_MAX_ROWS}")
+    fixed = {s.name: dataclasses.replace(s, pool=None if s.pool is None else list(s.pool))
+             for s in q.program.leaf_specs}
+    p = compile_query([], leaf_specs=fixed, trace=traced)
+    n = len(q.program.leaf_nodes)
+    if not _same_leaves(q, p) or not np.array_equal(p.leaves[:8 * n], q.program.leaves[:8 * n]):
+        raise EngineError("profile program's leaf layout differs from the search program's")
+    if p.n_trace_rows != len(traced) or any(p.trace_map[t.id][1] != "N" for t in traced):
+        raise EngineError("profile program: a conjunct is not one trace row")
+    return p, [p.trace_map[t.id][0] for t in main], (p.trace_map[all_cong.id][0] if cong else None)
+
+
 def _combine_chunks(values: Dict[str, int], name: str, width: int) -> int:
     if name in values:
         return values[name]
@@ -729,6 +792,40 @@ class WitnessEngine:
                 setattr(w, field, value)
                 self.stats["hits"] += 1
             return w
+        finally:
+            dp.free()
+
+    def explain_miss(self, q: Query, count: Optional[int] = None, begin: int = 0) -> MissProfile:
+        """Why candidates [begin, begin+count) of ``q`` hold no witness: how
+        many fail each conjunct, how many are rejected by that conjunct alone,
+        and the candidate that comes closest (:class:`MissProfile`), in one
+        call and one synchronisation (mg_search_blame).  The program checks
+        nothing and traces each conjunct's truth, on q.program's leaf layout,
+        so candidate i is the assignment ``search`` checks at i.  Conjunct
+        numbers are q.conjuncts' (see MissProfile).  Raises Unsupported for
+        more than 1024 conjunct rows and on a device without ``search_blame``
+        (a multi-device engine)."""
+        if not hasattr(self.dev, "search_blame"):
+            raise Unsupported("this device has no search_blame")
+        p, rows, crow = _profile_program(q)
+        count = count or self.launch_count([q])
+        dp = self.dev.load(p)
+        try:
+            fail, sole, satisfied, near, nfail, st = self.dev.search_blame(dp, self.seed, begin, count, 0,
+                                                                           p.n_trace_rows)
+            self.stats["evals"] += st["evals"]
+            self.stats["kernel_ms"] += st["kernel_ms"]
+            _, tr = self.dev.eval_generated(dp, self.seed, near, 1)
+            failed = [j for j, r in enumerate(rows) if not int(tr[r, 0])]
+            if crow is not None and not int(tr[crow, 0]):
+                failed.append(CONGRUENCE)
+            same = len(p.leaf_nodes) == len(q.program.leaf_nodes)
+            return MissProfile(count=count, satisfied=satisfied, fail=[fail[r] for r in rows],
+                               sole=[sole[r] for r in rows],
+                               congruence_fail=None if crow is None else fail[crow],
+                               congruence_sole=None if crow is None else sole[crow],
+                               nearest=self.materialize(q, near, dp if same else None), nearest_nfail=nfail,
+                               nearest_failed=failed, stats=st)
         finally:
             dp.free()
 

@@ -86,6 +86,35 @@ def search_lexmin(p: Program, seed: int, begin: int, n: int, objs, chunk: int = 
     return best[-1], list(best[:-1])
 
 
+def search_blame(p: Program, seed: int, begin: int, n: int, row: int, nrows: int, chunk: int = 1 << 14):
+    """(fail, sole, satisfied, near_index, near_nfail) over generated
+    candidates [begin, begin+n): p's trace rows [row, row+nrows) each hold one
+    conjunct's truth (0: failed); fail[j] counts the candidates failing row j,
+    sole[j] those failing row j alone, satisfied those failing none, and
+    near_index is the candidate failing the fewest rows (near_nfail), ties to
+    the lowest index.  The CPU twin of mg_search_blame, numpy over
+    eval_generated's rows; p's own verdict is ignored."""
+    if n <= 0 or begin < 0 or begin + n > 1 << 64:
+        raise RuntimeError("search_blame: a non-empty range")
+    if not 1 <= nrows <= 1024 or row < 0 or row + nrows > p.n_trace_rows:
+        raise RuntimeError("search_blame: 1 to 1024 of the program's trace rows")
+    fail = np.zeros(nrows, dtype=np.int64)
+    sole = np.zeros(nrows, dtype=np.int64)
+    satisfied, near = 0, None
+    for at in range(0, n, chunk):
+        m = min(chunk, n - at)
+        _, tr = eval_generated(p, seed, begin + at, m)
+        failed = tr[row:row + nrows] == 0
+        nfail = failed.sum(axis=0)
+        fail += failed.sum(axis=1)
+        sole += failed[:, nfail == 1].sum(axis=1)
+        satisfied += int((nfail == 0).sum())
+        j = int(np.argmin(nfail))          # the first of the lowest
+        if near is None or int(nfail[j]) < near[0]:
+            near = (int(nfail[j]), begin + at + j)
+    return [int(x) for x in fail], [int(x) for x in sole], satisfied, near[1], near[0]
+
+
 def eval_generated(p: Program, seed: int, begin: int, n: int):
     """Verdicts and trace rows of generated candidates [begin, begin+n) (host build)."""
     d, keep = make_desc(p)

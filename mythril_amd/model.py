@@ -147,6 +147,25 @@ def _solver_log(constraints, minimize, maximize, args, timeout):
         f.write(s.sexpr())
 
 
+# MYTHRIL_AMD_MISS_PROFILE=1: after a single-query miss, profile its first
+# candidates (WitnessEngine.explain_miss) and log the conjunct that blocks
+# them.  A diagnostic: no result changes, z3 answers the query as before.
+MISS_PROFILE = os.environ.get("MYTHRIL_AMD_MISS_PROFILE", "0") == "1"
+MISS_PROFILE_MAX = 1 << 16
+
+
+def _profile_miss(eng, q) -> None:
+    try:
+        m = eng.explain_miss(q, count=min(eng.budget, MISS_PROFILE_MAX))
+        STATS["miss_profiles"] = STATS.get("miss_profiles", 0) + 1
+        top = m.blocking()[0]
+        s, f = (m.congruence_sole, m.congruence_fail) if top < 0 else (m.sole[top], m.fail[top])
+        log.info("witness engine: miss of %d candidates: conjunct %s blocks (sole %d, fail %d); the nearest "
+                 "candidate fails %d", m.count, "congruence" if top < 0 else top, s, f, m.nearest_nfail)
+    except Exception as e:   # noqa: BLE001 - as around the search: a diagnostic never escapes
+        log.debug("witness engine: miss profile failed (%s)", e)
+
+
 def _gpu_model(constraints, timeout):
     from . import z3bridge
     from .runtime import EngineError
@@ -194,6 +213,8 @@ def _gpu_model(constraints, timeout):
             return None
         if witness is None:
             _record_miss(raws, key)
+            if MISS_PROFILE:
+                _profile_miss(eng, q)
     if witness is None:
         return None
     STATS["gpu_witnesses"] += 1

@@ -8,7 +8,10 @@ formulas outside the vocabulary fall back — and searches the rest on the
 device, many programs per launch.  It gives offline replays and benchmarks of
 real analyses without z3 or solc.
 
-    python -m mythril_amd.replay DIR [--budget 2^22] [--batch 64]
+    python -m mythril_amd.replay DIR [--budget 2^22] [--batch 64] [--explain-misses]
+
+``--explain-misses`` profiles every missed query (WitnessEngine.explain_miss)
+and prints one more line for it: which conjuncts reject its candidates.
 """
 from __future__ import annotations
 
@@ -33,6 +36,7 @@ class Result:
     reason: str = ""
     arrays: dict = field(default_factory=dict)      # array -> {index: value} (Ackermann leaves)
     functions: dict = field(default_factory=dict)   # UF -> {args: value}
+    profile: Optional[object] = None                # a miss under explain: engine.MissProfile (or the error's text)
 
 
 def load(path: str):
@@ -44,7 +48,26 @@ def load(path: str):
     return s, prepare(s.asserts, s.ctx), ""
 
 
-def replay(paths: List[str], engine, batch: int = 64) -> List[Result]:
+EXPLAIN_MAX = 1 << 16   # candidates of a miss profile
+
+
+def explain_line(r: Result) -> str:
+    """One line for a profiled miss: the query, how many candidates satisfied
+    everything, how many conjuncts the nearest one fails, and the three most
+    blocking conjuncts as number:sole/fail (c: the congruence conjuncts)."""
+    name = os.path.basename(r.path)
+    m = r.profile
+    if m is None or isinstance(m, str):
+        return f"miss {name}: no profile ({m})"
+    top = []
+    for j in m.blocking()[:3]:
+        s, f = (m.congruence_sole, m.congruence_fail) if j < 0 else (m.sole[j], m.fail[j])
+        top.append(f"{'c' if j < 0 else j}:{s}/{f}")
+    return (f"miss {name}: satisfied {m.satisfied}/{m.count}, nearest fails {m.nearest_nfail}, "
+            f"blocking (conjunct:sole/fail) {' '.join(top)}")
+
+
+def replay(paths: List[str], engine, batch: int = 64, explain: bool = False) -> List[Result]:
     out: List[Result] = []
     pending = []
     for p in paths:
@@ -63,6 +86,11 @@ def replay(paths: List[str], engine, batch: int = 64) -> List[Result]:
         for (p, s, q), w in zip(chunk, found):
             if w is None:
                 out.append(Result(p, "miss"))
+                if explain:
+                    try:
+                        out[-1].profile = engine.explain_miss(q, count=min(engine.budget, EXPLAIN_MAX))
+                    except Exception as e:   # noqa: BLE001 - a diagnostic: the miss stands
+                        out[-1].profile = f"{type(e).__name__}: {e}"
             else:
                 out.append(Result(p, "witness", w.index, dict(w.values), arrays=w.arrays, functions=w.functions))
     order = {p: k for k, p in enumerate(paths)}
@@ -75,6 +103,8 @@ def main(argv=None):
     ap.add_argument("--budget", type=int, default=1 << 22, help="candidates per query")
     ap.add_argument("--batch", type=int, default=64, help="programs per launch")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--explain-misses", action="store_true",
+                    help="profile every missed query: one line with its blocking conjuncts")
     a = ap.parse_args(argv)
     files = []
     for p in a.paths:
@@ -83,11 +113,13 @@ def main(argv=None):
     from .engine import WitnessEngine
     eng = WitnessEngine(device=a.device, budget=a.budget)
     t0 = time.perf_counter()
-    res = replay(files, eng, a.batch)
+    res = replay(files, eng, a.batch, explain=a.explain_misses)
     dt = time.perf_counter() - t0
     for r in res:
         print(json.dumps({"file": os.path.basename(r.path), "status": r.status, "index": r.index,
                           "reason": r.reason}))
+        if a.explain_misses and r.status == "miss":
+            print(explain_line(r))
     summary = {k: sum(1 for r in res if r.status == k) for k in ("witness", "miss", "z3", "unsupported")}
     print(json.dumps({"files": len(res), **summary, "seconds": dt, "engine": eng.stats}), flush=True)
     eng.close()

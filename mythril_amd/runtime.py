@@ -81,6 +81,12 @@ class MgLexResult(ctypes.Structure):
         return int(self.index), [sum(int(v) << (32 * k) for k, v in enumerate(self.value[j])) for j in range(nobj)]
 
 
+class MgBlameResult(ctypes.Structure):
+    """include/mythril_witness.h mg_blame_result"""
+    _fields_ = [("satisfied", ctypes.c_uint64), ("near_index", ctypes.c_uint64), ("near_nfail", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
 _P = ctypes.c_void_p
 _lib = None
 _lib_lock = threading.Lock()
@@ -110,6 +116,10 @@ SIGNATURES = {
                                         ctypes.POINTER(MgLexResult), ctypes.POINTER(MgStats)]),
     "mg_search_lexmin_tile": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64,
                                              ctypes.POINTER(ctypes.c_uint64)]),
+    "mg_search_blame": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
+                                       ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                                       ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(MgBlameResult),
+                                       ctypes.POINTER(MgStats)]),
     "mg_eval": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t, _P, _P]),
     "mg_eval_generated": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t, _P, _P]),
     "mg_witness_leaves": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, _P]),
@@ -323,6 +333,27 @@ class Device:
         _check(self.lib, self.lib.mg_search_lexmin_tile(self.handle, dp.handle, count, tile, ctypes.byref(out)),
                "mg_search_lexmin_tile")
         return int(out.value)
+
+    def search_blame(self, dp: DeviceProgram, seed: int, begin: int, count: int, row: int, nrows: int,
+                     tile: int = 0) -> Tuple[List[int], List[int], int, int, int, dict]:
+        """mg_search_blame: (fail, sole, satisfied, near_index, near_nfail,
+        stats) over candidates [begin, begin+count), where dp's trace rows
+        [row, row+nrows) each hold one conjunct's truth (0: failed).  fail[j]
+        counts the candidates that fail row j, sole[j] those that fail row j
+        and no other, satisfied those that fail none; near_index is the
+        candidate that fails the fewest rows (near_nfail of them), ties to the
+        lowest index.  tile: as search_lexmin's."""
+        if self._reap_queue:
+            self._reap()
+        fail = (ctypes.c_uint64 * max(1, nrows))()
+        sole = (ctypes.c_uint64 * max(1, nrows))()
+        out = MgBlameResult()
+        st = MgStats()
+        _check(self.lib, self.lib.mg_search_blame(self.handle, dp.handle, seed & ((1 << 64) - 1), begin, count, row,
+                                                  nrows, tile, fail, sole, ctypes.byref(out), ctypes.byref(st)),
+               "mg_search_blame")
+        return ([int(v) for v in fail[:nrows]], [int(v) for v in sole[:nrows]], int(out.satisfied),
+                int(out.near_index), int(out.near_nfail), st.as_dict())
 
     def search_begin(self, progs: Sequence[DeviceProgram], seed: int, begin: int, count: int,
                      flags: int = 0) -> None:
