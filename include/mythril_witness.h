@@ -212,6 +212,44 @@ int mg_search_blame(mg_ctx* ctx, mg_prog* prog, uint64_t seed, uint64_t begin, u
                     uint64_t* out_fail, uint64_t* out_sole,   /* nrows each */
                     mg_blame_result* out, mg_stats* stats);
 
+typedef struct {
+  uint64_t total;          /* candidates of the range whose verdict is 1 */
+  uint32_t stored;         /* min(total, cap): entries written to out_idx (and out_rows) */
+  uint32_t reserved;
+} mg_collect_result;
+/* Which candidates are witnesses, and how many: over candidates
+ * [begin, begin+count), out->total is the exact number whose verdict is 1,
+ * out_idx[0..stored) are the stored = min(total, cap) lowest witness indices
+ * in ascending order, and out_rows[k * nrows + r] is trace row row + r of
+ * witness k.  nrows == 0 gathers nothing: out_rows is ignored (may be NULL)
+ * and a program without trace rows is accepted.  Entries past `stored` are
+ * left untouched.  Every result is exact and depends on neither grid, tile
+ * nor engine.  The range is cut into tiles by mg_search_lexmin's rule
+ * (mg_search_lexmin_tile answers for this call too) and each tile is
+ * evaluated with its trace rows on the engine mg_eval_generated uses when a
+ * trace is asked for (the asm interpreter where it runs the program, else the
+ * compiled one; no attached kernel).  Two kernels then fold the tile, in
+ * candidate order: one counts the witnesses of each fold block's contiguous
+ * segment, one places them behind those of the blocks and tiles before (an
+ * order-preserving compaction; ordering comes from kernel boundaries alone,
+ * no block waits for another and nothing is atomic).  The whole range is
+ * always evaluated: stats->evals == count, stats->launches == 3 * tiles, one
+ * upload and one synchronisation; the readback is 16 + cap * (8 + 4 * nrows)
+ * bytes.  Refused with MG_E_ARG for a null out or out_idx, cap of 0 or above
+ * 65536, nrows above 64, nrows > 0 with a null out_rows, rows outside the
+ * program's trace, count == 0 or a wrapping range, a tile that is no multiple
+ * of 256, more than 65536 tiles, and while a search begun with
+ * mg_search_begin is pending.  Same handle, lock and in-flight protocol as
+ * mg_search_blame.  Replaces nothing in the reference: z3's Optimize.model()
+ * yields one model (mythril/support/model.py:58-60) and never a count.  For
+ * callers that want a second witness when the first is rejected
+ * (WitnessEngine.search_all). */
+int mg_search_collect(mg_ctx* ctx, mg_prog* prog, uint64_t seed, uint64_t begin, uint64_t count,
+                      uint32_t row, uint32_t nrows, uint64_t tile,
+                      uint64_t* out_idx,    /* cap */
+                      uint32_t* out_rows,   /* cap * nrows, witness-major */
+                      size_t cap, mg_collect_result* out, mg_stats* stats);
+
 /* Evaluate one program on explicit assignments: leaves_soa has n_input_rows
  * rows of ncand u32 (row r, candidate i at [r*ncand + i]).  verdict[i] = 0/1;
  * trace (may be NULL) receives n_trace_rows rows of ncand u32. */

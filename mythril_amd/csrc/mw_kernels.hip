@@ -32,6 +32,7 @@
 #include "mw_asm_abi.h"
 #include "mw_asm_interp.inc"
 #include "mw_blame.h"
+#include "mw_collect.h"
 #include "mw_handles.h"
 #include "mw_inflight.h"
 #include "mw_interp.h"
@@ -516,6 +517,96 @@ __global__ __launch_bounds__(kBlock) void mw_blame_fold_kernel(const u32* __rest
   }
   for (u32 i = threadIdx.x; i < nbins; i += kBlock)
     if (bins[i]) atomicAdd(&totals[i], (unsigned long long)bins[i]);
+}
+
+// mg_search_collect's first kernel per tile: block b counts the witnesses of
+// its segment of the tile's n verdicts (mw_collect.h collect_segment: contiguous
+// segments in block order, not a grid stride, because positions follow
+// candidate order) into cnt[b].  Every lane of a wave adds the popcount of the
+// wave's ballot, the four wave totals meet in LDS.  The chunk loop is uniform
+// over the block: every lane reaches every ballot, and a lane at or past the
+// segment's end is false in all of them.
+__global__ __launch_bounds__(kBlock) void mw_collect_count_kernel(const u32* __restrict__ verdict, u32 n,
+                                                                   u32* __restrict__ cnt) {
+  __shared__ u32 wave_total[kCollectWaves];
+  const u32 seg = collect_segment(n, gridDim.x);
+  const u32 lo = collect_seg_begin(blockIdx.x, seg, n), hi = collect_seg_end(blockIdx.x, seg, n);
+  u32 mine = 0;   // the wave's count, the same in every lane
+  for (u32 j0 = lo; j0 < hi; j0 += kCollectChunk) {
+    const u32 j = j0 + threadIdx.x;
+    const bool w = j < hi && collect_is_witness(verdict[j]);
+    mine += collect_wave_total(__ballot(w));
+  }
+  if ((threadIdx.x & 63u) == 0u) wave_total[threadIdx.x >> 6] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u32 all = 0;
+#pragma unroll
+    for (u32 k = 0; k < kCollectWaves; ++k) all += wave_total[k];
+    cnt[blockIdx.x] = all;
+  }
+}
+
+// ... and its second: block b places the witnesses of the same segment at the
+// call's positions pos, pos + 1, .. in candidate order, where pos is the
+// running base of the tiles before (base[slot]) plus the counts of the blocks
+// before it (the block sums cnt[0..b) itself: at most kLexMaxFoldBlocks
+// words).  A witness's rank within the block is the chunks before (run), the
+// waves of its chunk before (wave totals through LDS, two alternating rows so
+// that one barrier per chunk is enough) and the lanes of its wave before
+// (collect_lane_rank on the ballot).  For every rank below cap the thread
+// stores the candidate's index and gathers its nrows row words (row r of tile
+// offset j at trace[r * stride + j]).  The last block stores the next tile's
+// base, base[slot ^ 1] = base[slot] + the tile's count, a slot no block of
+// this launch reads.  A block whose position is at or past cap returns before
+// it reads a verdict, and a block stops once its chunks have passed cap.
+// Ordering comes from the kernel boundaries of the one stream alone: no block
+// waits for another, nothing is atomic.
+__global__ __launch_bounds__(kBlock) void mw_collect_scatter_kernel(const u32* __restrict__ verdict,
+                                                                     const u32* __restrict__ trace, u64 stride, u32 n,
+                                                                     u64 tile_begin, const u32* __restrict__ cnt,
+                                                                     u64* __restrict__ base, u32 slot, u32 cap, u32 row,
+                                                                     u32 nrows, u64* __restrict__ out_idx,
+                                                                     u32* __restrict__ out_rows) {
+  __shared__ u32 wave_total[2][kCollectWaves];
+  __shared__ u64 wave_sum[kCollectWaves];
+  const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  // the counts of the blocks before this one
+  u64 before = 0;
+  for (u32 i = threadIdx.x; i < blockIdx.x; i += kBlock) before += cnt[i];
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) before += (u64)__shfl_xor((unsigned long long)before, m);
+  if (lane == 0u) wave_sum[wave] = before;
+  __syncthreads();
+  u64 prefix = 0;
+#pragma unroll
+  for (u32 k = 0; k < kCollectWaves; ++k) prefix += wave_sum[k];
+  const u64 pos = collect_block_pos(base[slot & 1u], prefix);
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) base[(slot & 1u) ^ 1u] = pos + cnt[blockIdx.x];
+  if (pos >= cap) return;   // uniform over the block
+  const u32 seg = collect_segment(n, gridDim.x);
+  const u32 lo = collect_seg_begin(blockIdx.x, seg, n), hi = collect_seg_end(blockIdx.x, seg, n);
+  u32 run = 0, flip = 0;
+  for (u32 j0 = lo; j0 < hi && pos + run < cap; j0 += kCollectChunk, flip ^= 1u) {
+    const u32 j = j0 + threadIdx.x;
+    const bool w = j < hi && collect_is_witness(verdict[j]);
+    const u64 ballot = __ballot(w);
+    if (lane == 0u) wave_total[flip][wave] = collect_wave_total(ballot);
+    __syncthreads();   // (the row written two chunks ago was read before the barrier of the chunk between)
+    u32 wave_off = 0, chunk = 0;
+#pragma unroll
+    for (u32 k = 0; k < kCollectWaves; ++k) {
+      const u32 t = wave_total[flip][k];
+      wave_off += k < wave ? t : 0u;
+      chunk += t;
+    }
+    const u64 rank = collect_rank(pos, run, wave_off, collect_lane_rank(ballot, lane));
+    if (w && rank < cap) {
+      out_idx[rank] = tile_begin + j;
+      for (u32 r = 0; r < nrows; ++r) out_rows[rank * nrows + r] = trace[(u64)(row + r) * stride + j];
+    }
+    run += chunk;
+  }
 }
 
 // Threaded-dispatch interpreter (mythril_amd/asmgen.py -> mw_asm_interp.inc):
@@ -2255,7 +2346,8 @@ static LexPlan lexmin_plan(const Ctx* c, const Prog* p, u64 count, u64 tile, u32
                             wide_lds_words());
 }
 
-// The tiles of mg_search_lexmin and mg_search_blame (the context's mu held):
+// The tiles of mg_search_lexmin, mg_search_blame and mg_search_collect
+// (mw_collect.inc: its program may have no trace rows), the context's mu held:
 // the launch block and the spill buffer sized (one AsmArgs record per tile on
 // the asm interpreter, then `extra`'s n_extra records, which land at
 // c->d_asmargs + tile_records(L)), the call's one upload, init() for the memsets
@@ -2291,7 +2383,7 @@ static int tiles_enqueue(Ctx* c, const Prog* p, uint64_t seed, uint64_t begin, u
   HIPCHK(hipEventRecord(c->e0, c->stream));
   for (u64 t = 0; t < L.ntiles; ++t) {
     const u64 n = tile_n(t), tb = begin + t * L.tile;
-    if (!p->trace_full) HIPCHK(hipMemsetAsync(d_t, 0, (size_t)nrows * n * 4, c->stream));
+    if (nrows && !p->trace_full) HIPCHK(hipMemsetAsync(d_t, 0, (size_t)nrows * n * 4, c->stream));
     if (on_asm) {
       rc = launch_eval_asm(c, p, false, c->d_asmargs + t, tile_gx(n), L.nlds);
       if (rc) return rc;
@@ -2464,6 +2556,8 @@ int mg_search_blame(mg_ctx* h, mg_prog* hp, uint64_t seed, uint64_t begin, uint6
   const u64 ev[kNCounters] = {B.tiles.engine.kind == kAsm ? ctr[0] : count, 0, 0, 0, 0};
   return fill_stats(c, st, ev, t0, B.nlaunches, (double)ev[0] * (double)p->ops_per_eval);
 }
+
+#include "mw_collect.inc"   // mg_search_collect: the tiles again, a count and a scatter kernel per tile
 
 // One-shot evaluation of a program that is not kept (a witness program:
 // engine.WitnessEngine._materialize_traced): upload, evaluation and release

@@ -361,4 +361,32 @@ inline BlamePlan plan_search_blame(const ProgFacts& facts, u64 count, u64 tile, 
   return B;
 }
 
+// mg_search_collect: plan_search_lexmin's tiles, engine and fold grid again
+// (mg_search_lexmin_tile answers for this call too).  After a tile's
+// evaluation mw_collect_count_kernel writes one count per fold block and
+// mw_collect_scatter_kernel places the tile's witnesses behind those of the
+// tiles before: 3 launches per tile, no reduction kernel.  The result block is
+// mw_collect.h's (two u64 base slots, cap indices, cap * nrows row words), read
+// back whole; the blocks' counts follow it on the device.
+struct CollectPlan {
+  LexPlan tiles;              // tile, ntiles (0: refused), fold_gx, engine, eval_gx, nlds, scratch_bytes, spill_need
+  size_t count_bytes = 0;     // one u32 per fold block
+  size_t out_bytes = 0;       // the result block
+  size_t readback_bytes = 0;  // all of it
+  size_t buffer_bytes = 0;    // the result block, then the counts
+  size_t nlaunches = 0;       // 3 per tile
+};
+
+inline CollectPlan plan_search_collect(const ProgFacts& facts, u64 count, u64 tile, u32 cap, u32 nrows, u32 n_trace_rows,
+                                       int ncu, bool use_asm, u32 wide_words) {
+  CollectPlan C;
+  C.tiles = plan_search_lexmin(facts, count, tile, 0, n_trace_rows, ncu, use_asm, wide_words);
+  C.count_bytes = (size_t)C.tiles.fold_gx * sizeof(u32);
+  C.out_bytes = 2 * sizeof(u64) + (size_t)cap * sizeof(u64) + (size_t)cap * nrows * sizeof(u32);
+  C.readback_bytes = C.out_bytes;
+  C.buffer_bytes = C.out_bytes + C.count_bytes;
+  C.nlaunches = (size_t)(3 * C.tiles.ntiles);
+  return C;
+}
+
 }  // namespace mw

@@ -545,6 +545,7 @@ def _objectives_program(q: "Query", objectives: Sequence[Node]) -> Program:
 
 
 BLAME_MAX_ROWS = 1024     # include/mythril_witness.h mg_search_blame (csrc/mw_blame.h kBlameMaxRows)
+COLLECT_MAX = 65536       # include/mythril_witness.h mg_search_collect (csrc/mw_collect.h kCollectMaxCap)
 CONGRUENCE = -1           # MissProfile: the congruence conjuncts' one bin, where conjunct numbers are listed
 
 
@@ -826,6 +827,35 @@ class WitnessEngine:
                                congruence_sole=None if crow is None else sole[crow],
                                nearest=self.materialize(q, near, dp if same else None), nearest_nfail=nfail,
                                nearest_failed=failed, stats=st)
+        finally:
+            dp.free()
+
+    def search_all(self, q: Query, limit: int, count: Optional[int] = None,
+                   begin: int = 0) -> Tuple[List[Witness], int]:
+        """(witnesses, total): the ``limit`` lowest witnesses of ``q`` among
+        candidates [begin, begin+count), in index order, and the exact number
+        of witnesses the range holds, in one call and one synchronisation
+        (mg_search_collect on q.program: no rows are gathered).  The whole
+        range is evaluated, where ``search`` stops at its first hit.  Each
+        index is materialised as ``search`` does it; like every witness these
+        are not re-evaluated here.  Raises Unsupported for a limit outside
+        1..65536 and on a device without ``search_collect`` (a multi-device
+        engine)."""
+        if not hasattr(self.dev, "search_collect"):
+            raise Unsupported("this device has no search_collect")
+        if not 1 <= limit <= COLLECT_MAX:
+            raise Unsupported(f"a limit of {limit} witnesses: 1 to {COLLECT_MAX}")
+        count = count or self.launch_count([q])
+        dp = self.dev.load(q.program)
+        try:
+            indices, _, total, st = self.dev.search_collect(dp, self.seed, begin, count, limit)
+            self.stats["searches"] += 1
+            self.stats["programs"] += 1
+            self.stats["evals"] += st["evals"]
+            self.stats["kernel_ms"] += st["kernel_ms"]
+            found = [w for w in (self.materialize(q, idx, dp) for idx in indices) if w is not None]
+            self.stats["hits"] += 1 if found else 0
+            return found, total
         finally:
             dp.free()
 

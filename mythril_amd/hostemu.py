@@ -115,6 +115,35 @@ def search_blame(p: Program, seed: int, begin: int, n: int, row: int, nrows: int
     return [int(x) for x in fail], [int(x) for x in sole], satisfied, near[1], near[0]
 
 
+def search_collect(p: Program, seed: int, begin: int, n: int, cap: int, row: int = 0, nrows: int = 0,
+                   chunk: int = 1 << 14):
+    """(indices, rows, total) over generated candidates [begin, begin+n): total
+    is the number whose verdict is 1, indices the min(total, cap) lowest of
+    them in ascending order, rows a (len(indices), nrows) uint32 array with p's
+    trace rows [row, row+nrows) of each.  The CPU twin of mg_search_collect,
+    numpy over eval_generated; the same refusals."""
+    if n <= 0 or begin < 0 or begin + n > 1 << 64:
+        raise RuntimeError("search_collect: a non-empty range")
+    if not 1 <= cap <= 65536:
+        raise RuntimeError("search_collect: room for 1 to 65536 witnesses")
+    if not 0 <= nrows <= 64 or (nrows and (row < 0 or row + nrows > p.n_trace_rows)):
+        raise RuntimeError("search_collect: at most 64 of the program's trace rows")
+    total = 0
+    indices: list = []
+    rows = []
+    for at in range(0, n, chunk):
+        m = min(chunk, n - at)
+        v, tr = eval_generated(p, seed, begin + at, m)
+        hit = np.flatnonzero(v)
+        total += int(hit.size)
+        keep = hit[:cap - len(indices)]
+        indices.extend(begin + at + int(j) for j in keep)
+        if nrows and keep.size:
+            rows.append(np.asarray(tr)[row:row + nrows][:, keep].T)
+    out = np.concatenate(rows).astype(np.uint32) if rows else np.zeros((len(indices), nrows), dtype=np.uint32)
+    return indices, out, total
+
+
 def eval_generated(p: Program, seed: int, begin: int, n: int):
     """Verdicts and trace rows of generated candidates [begin, begin+n) (host build)."""
     d, keep = make_desc(p)

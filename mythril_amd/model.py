@@ -154,6 +154,15 @@ MISS_PROFILE = os.environ.get("MYTHRIL_AMD_MISS_PROFILE", "0") == "1"
 MISS_PROFILE_MAX = 1 << 16
 
 
+# MYTHRIL_AMD_WITNESS_RETRIES=N: the fresh single-query search collects its N+1
+# lowest witnesses (WitnessEngine.search_all, mg_search_collect: the whole
+# range evaluated) and z3 re-checks them in index order until it confirms one;
+# the reference answers only after all of them failed.  0 (the default): one
+# witness from the early-exit search, as before.  Memo hits are not affected.
+WITNESS_RETRIES = max(0, int(os.environ.get("MYTHRIL_AMD_WITNESS_RETRIES", "0")))
+WITNESS_RETRIES_MAX = 1 << 16   # mg_search_collect's room
+
+
 def _profile_miss(eng, q) -> None:
     try:
         m = eng.explain_miss(q, count=min(eng.budget, MISS_PROFILE_MAX))
@@ -171,6 +180,7 @@ def _gpu_model(constraints, timeout):
     from .runtime import EngineError
     raws = [c.raw for c in constraints]
     key = memo_key(raws)
+    spares = []   # MYTHRIL_AMD_WITNESS_RETRIES: the search's further witnesses, in index order
     hit = _memo_get(raws, key)
     if hit is None and _pending:
         # the JUMPI successors LASER is about to prune one by one (svm.py:287-292):
@@ -204,7 +214,12 @@ def _gpu_model(constraints, timeout):
             return None
         STATS["gpu_attempts"] += 1
         try:
-            witness = eng.search([q])[0]
+            if WITNESS_RETRIES and hasattr(eng.dev, "search_collect"):
+                # the whole range evaluated once: its lowest witnesses, in index order
+                found, _ = eng.search_all(q, min(WITNESS_RETRIES + 1, WITNESS_RETRIES_MAX))
+                witness, spares = (found[0], found[1:]) if found else (None, [])
+            else:
+                witness = eng.search([q])[0]
         except EngineError as e:
             # a device-side failure (validation, allocation, launch) never escapes:
             # the reference answers, exactly as without the engine
@@ -218,12 +233,18 @@ def _gpu_model(constraints, timeout):
     if witness is None:
         return None
     STATS["gpu_witnesses"] += 1
-    try:
-        zm, slow = z3bridge.recheck(raws, script, witness, timeout, PINNED_CHECK_MS)
-    except Exception as e:   # fail closed: the reference answers
-        STATS["recheck_errors"] = STATS.get("recheck_errors", 0) + 1
-        log.warning("witness engine: z3 re-check failed (%s); z3 answers", e)
-        return None
+    zm, slow = None, False
+    for k, w in enumerate([witness] + spares):
+        if k:   # MYTHRIL_AMD_WITNESS_RETRIES: the next witness of the same search
+            STATS["witness_retries"] = STATS.get("witness_retries", 0) + 1
+        try:
+            zm, slow = z3bridge.recheck(raws, script, w, timeout, PINNED_CHECK_MS)
+        except Exception as e:   # fail closed: the reference answers
+            STATS["recheck_errors"] = STATS.get("recheck_errors", 0) + 1
+            log.warning("witness engine: z3 re-check failed (%s); z3 answers", e)
+            zm = None
+        if zm is not None:
+            break
     if zm is None:
         return None
     if slow:

@@ -8,10 +8,13 @@ formulas outside the vocabulary fall back — and searches the rest on the
 device, many programs per launch.  It gives offline replays and benchmarks of
 real analyses without z3 or solc.
 
-    python -m mythril_amd.replay DIR [--budget 2^22] [--batch 64] [--explain-misses]
+    python -m mythril_amd.replay DIR [--budget 2^22] [--batch 64] [--explain-misses] [--witness-density]
 
 ``--explain-misses`` profiles every missed query (WitnessEngine.explain_miss)
 and prints one more line for it: which conjuncts reject its candidates.
+``--witness-density`` counts every searched query's witnesses
+(WitnessEngine.search_all) and prints one more line for it: how many of its
+candidates are witnesses, and the first of them.
 """
 from __future__ import annotations
 
@@ -37,6 +40,7 @@ class Result:
     arrays: dict = field(default_factory=dict)      # array -> {index: value} (Ackermann leaves)
     functions: dict = field(default_factory=dict)   # UF -> {args: value}
     profile: Optional[object] = None                # a miss under explain: engine.MissProfile (or the error's text)
+    density: Optional[object] = None                # under density: (total, count, first index or None) (or the error's text)
 
 
 def load(path: str):
@@ -67,7 +71,18 @@ def explain_line(r: Result) -> str:
             f"blocking (conjunct:sole/fail) {' '.join(top)}")
 
 
-def replay(paths: List[str], engine, batch: int = 64, explain: bool = False) -> List[Result]:
+def density_line(r: Result) -> str:
+    """One line for a counted query: how many of its candidates are witnesses
+    (total / count) and the lowest witness index."""
+    name = os.path.basename(r.path)
+    d = r.density
+    if d is None or isinstance(d, str):
+        return f"density {name}: not counted ({d})"
+    total, count, first = d
+    return f"density {name}: {total} / {count} witnesses, first {'none' if first is None else first}"
+
+
+def replay(paths: List[str], engine, batch: int = 64, explain: bool = False, density: bool = False) -> List[Result]:
     out: List[Result] = []
     pending = []
     for p in paths:
@@ -93,6 +108,13 @@ def replay(paths: List[str], engine, batch: int = 64, explain: bool = False) -> 
                         out[-1].profile = f"{type(e).__name__}: {e}"
             else:
                 out.append(Result(p, "witness", w.index, dict(w.values), arrays=w.arrays, functions=w.functions))
+            if density:
+                try:
+                    n = engine.launch_count([q])
+                    some, total = engine.search_all(q, 1, count=n)
+                    out[-1].density = (total, n, some[0].index if some else None)
+                except Exception as e:   # noqa: BLE001 - a diagnostic: the result stands
+                    out[-1].density = f"{type(e).__name__}: {e}"
     order = {p: k for k, p in enumerate(paths)}
     return sorted(out, key=lambda r: order[r.path])
 
@@ -105,6 +127,8 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--explain-misses", action="store_true",
                     help="profile every missed query: one line with its blocking conjuncts")
+    ap.add_argument("--witness-density", action="store_true",
+                    help="count every searched query's witnesses: one line with total / count and the first index")
     a = ap.parse_args(argv)
     files = []
     for p in a.paths:
@@ -113,13 +137,15 @@ def main(argv=None):
     from .engine import WitnessEngine
     eng = WitnessEngine(device=a.device, budget=a.budget)
     t0 = time.perf_counter()
-    res = replay(files, eng, a.batch, explain=a.explain_misses)
+    res = replay(files, eng, a.batch, explain=a.explain_misses, density=a.witness_density)
     dt = time.perf_counter() - t0
     for r in res:
         print(json.dumps({"file": os.path.basename(r.path), "status": r.status, "index": r.index,
                           "reason": r.reason}))
         if a.explain_misses and r.status == "miss":
             print(explain_line(r))
+        if a.witness_density and r.status in ("witness", "miss"):
+            print(density_line(r))
     summary = {k: sum(1 for r in res if r.status == k) for k in ("witness", "miss", "z3", "unsupported")}
     print(json.dumps({"files": len(res), **summary, "seconds": dt, "engine": eng.stats}), flush=True)
     eng.close()

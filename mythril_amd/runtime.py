@@ -87,6 +87,11 @@ class MgBlameResult(ctypes.Structure):
                 ("reserved", ctypes.c_uint32)]
 
 
+class MgCollectResult(ctypes.Structure):
+    """include/mythril_witness.h mg_collect_result"""
+    _fields_ = [("total", ctypes.c_uint64), ("stored", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 _P = ctypes.c_void_p
 _lib = None
 _lib_lock = threading.Lock()
@@ -120,6 +125,9 @@ SIGNATURES = {
                                        ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
                                        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(MgBlameResult),
                                        ctypes.POINTER(MgStats)]),
+    "mg_search_collect": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
+                                         ctypes.c_uint32, ctypes.c_uint64, _P, _P, ctypes.c_size_t,
+                                         ctypes.POINTER(MgCollectResult), ctypes.POINTER(MgStats)]),
     "mg_eval": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t, _P, _P]),
     "mg_eval_generated": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t, _P, _P]),
     "mg_witness_leaves": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, _P]),
@@ -354,6 +362,28 @@ class Device:
                "mg_search_blame")
         return ([int(v) for v in fail[:nrows]], [int(v) for v in sole[:nrows]], int(out.satisfied),
                 int(out.near_index), int(out.near_nfail), st.as_dict())
+
+    def search_collect(self, dp: DeviceProgram, seed: int, begin: int, count: int, cap: int, row: int = 0,
+                       nrows: int = 0, tile: int = 0) -> Tuple[List[int], np.ndarray, int, dict]:
+        """mg_search_collect: (indices, rows, total, stats) over candidates
+        [begin, begin+count).  total is the exact number of witnesses of the
+        range, indices the min(total, cap) lowest of them in ascending order,
+        rows a (len(indices), nrows) uint32 array with dp's trace rows
+        [row, row+nrows) of each.  The whole range is evaluated.  tile: as
+        search_lexmin's."""
+        if self._reap_queue:
+            self._reap()
+        room = cap if 0 < cap <= 65536 else 1          # the library refuses the cap itself
+        idx = np.zeros(room, dtype=np.uint64)
+        rows = np.zeros((room, nrows if 0 < nrows <= 64 else 0), dtype=np.uint32)
+        out = MgCollectResult()
+        st = MgStats()
+        _check(self.lib, self.lib.mg_search_collect(self.handle, dp.handle, seed & ((1 << 64) - 1), begin, count, row,
+                                                    nrows, tile, idx.ctypes.data, rows.ctypes.data if nrows else None,
+                                                    cap, ctypes.byref(out), ctypes.byref(st)),
+               "mg_search_collect")
+        k = int(out.stored)
+        return [int(v) for v in idx[:k]], rows[:k].copy(), int(out.total), st.as_dict()
 
     def search_begin(self, progs: Sequence[DeviceProgram], seed: int, begin: int, count: int,
                      flags: int = 0) -> None:
