@@ -250,6 +250,57 @@ int mg_search_collect(mg_ctx* ctx, mg_prog* prog, uint64_t seed, uint64_t begin,
                       uint32_t* out_rows,   /* cap * nrows, witness-major */
                       size_t cap, mg_collect_result* out, mg_stats* stats);
 
+typedef struct {
+  uint64_t index;          /* the nearest mutant: lowest (failed rows, index); never MG_NONE: count >= 1 */
+  uint32_t nfail;          /* rows it fails (0: it is a witness) */
+  uint32_t reserved;
+  uint64_t satisfied;      /* mutants failing no row */
+} mg_repair_result;
+/* Neighbourhood search around a near-miss: mutants [begin, begin+count) of an
+ * explicit base assignment, generated on the device and never stored.  base
+ * holds nleaves x 8 limbs in mg_witness_leaves' layout (each value is cut to
+ * its leaf's width); mutable_leaves names the nmut leaves (1..1024, indices
+ * strictly ascending) a mutant may change; radius (1..4) bounds how many of
+ * them it does.  With S the sum of the mutable leaves' widths, mutant m < S
+ * flips exactly one bit: bit m - prefix[s] of mutable leaf s, slots in order
+ * and bits ascending, so a witness one bit away from base within the mutable
+ * leaves is found by count >= S at a known index.  A mutant m >= S applies 1 to
+ * radius hashed picks of (leaf, flip a bit | add 2^b | subtract 2^b | replace
+ * by a pool entry or a random value); the rule is csrc/mw_mutate.h's, pure in
+ * (base, mutable_leaves, seed, radius, m).  Mutants are scored as
+ * mg_search_blame scores candidates: the program's trace rows [row, row+nrows)
+ * each hold one conjunct's truth (0: failed); with nrows == 0 the program's
+ * verdict is the one row.  out->index / out->nfail are the mutant of lowest
+ * (failed rows, index), out->satisfied counts the mutants that fail no row:
+ * one call either finds a witness (nfail == 0) or returns a nearer base to go
+ * on from.  The range is cut into tiles by mg_search_lexmin's rule; each tile
+ * is evaluated by mw_repair_kernel, always on the compiled interpreter (the
+ * other engines have no such mode), and folded by mg_search_blame's fold:
+ * stats->launches == 2 * tiles, stats->evals == count, one upload (the base,
+ * the mutable leaves and their prefix sums travel with the launch records)
+ * and one synchronisation.  Refused with MG_E_ARG for a null argument, a
+ * program without leaves, nmut of 0 or above 1024, a mutable leaf that is no
+ * leaf of the program or not above the one before, a radius outside 1..4,
+ * count == 0, a wrapping range, begin + count above 2^48, nrows above 1024,
+ * rows outside the program's trace, a tile that is no multiple of 256, more
+ * than 65536 tiles, and while a search begun with mg_search_begin is pending.
+ * Same handle, lock and in-flight protocol as mg_search_blame.  Replaces
+ * nothing in the reference: z3 answers a set it finds no model for with unsat
+ * or unknown (mythril/laser/smt/solver/solver.py:50-66) and offers no
+ * assignment to go on from (WitnessEngine.repair). */
+int mg_search_repair(mg_ctx* ctx, mg_prog* prog, const uint32_t* base, const uint32_t* mutable_leaves, size_t nmut,
+                     uint64_t seed, uint32_t radius, uint64_t begin, uint64_t count,
+                     uint32_t row, uint32_t nrows, uint64_t tile, mg_repair_result* out, mg_stats* stats);
+/* The leaf values of mutant `index` of the same base, mutable leaves, seed and
+ * radius: what the device evaluated at out->index, in mg_witness_leaves'
+ * layout (nleaves x 8 limbs).  Computed on the host from the leaf table and
+ * pool the library keeps of a loaded program: no launch, so it is allowed
+ * while a begun search is pending.  The same refusals for base,
+ * mutable_leaves, nmut and radius.  Replaces nothing in the reference
+ * (ModelRef.eval reads a model z3 found; this reads one the search built). */
+int mg_repair_leaves(mg_ctx* ctx, const mg_prog* prog, const uint32_t* base, const uint32_t* mutable_leaves,
+                     size_t nmut, uint64_t seed, uint32_t radius, uint64_t index, uint32_t* out /* nleaves x 8 */);
+
 /* Evaluate one program on explicit assignments: leaves_soa has n_input_rows
  * rows of ncand u32 (row r, candidate i at [r*ncand + i]).  verdict[i] = 0/1;
  * trace (may be NULL) receives n_trace_rows rows of ncand u32. */

@@ -25,7 +25,7 @@ DEVICE_SRCS = ["mw_kernels.hip", "mw_validate.cpp", "mw_compile.cpp"]
 HOST_SRCS = ["mw_host_emu.cpp", "mw_validate.cpp"]
 HEADERS = ["mw_isa.h", "mw_prog.h", "mw_alu.h", "mw_interp.h", "mw_leaf.h", "mw_keccak.h", "mw_asm_interp.inc",
            "mw_asm_abi.h", "mw_handles.h", "mw_inflight.h", "mw_launch_plan.h", "mw_min.h", "mw_lex.h",
-           "mw_blame.h", "mw_collect.h", "mw_collect.inc"]
+           "mw_blame.h", "mw_collect.h", "mw_collect.inc", "mw_mutate.h", "mw_repair.inc"]
 ASMJIT_TEMPLATE = ROOT / "mythril_amd" / "lib" / "asmjit_template.s"   # package data
 
 

@@ -15,6 +15,7 @@
 #include "mw_keccak.h"
 #include "mw_leaf.h"
 #include "mw_min.h"
+#include "mw_mutate.h"
 
 using namespace mw;
 
@@ -170,6 +171,23 @@ int mwh_leaf_values(const mg_prog_desc* d, uint64_t seed, uint64_t cand, uint32_
   int rc = mg_validate_desc(d);
   if (rc) return rc;
   for (size_t l = 0; l < d->nleaves; ++l) leaf_value(d->leaves + l * MW_LEAF_WORDS, d->pool, seed, cand, out + 8 * l);
+  return 0;
+}
+
+// Leaf values of mutant m of a base assignment (csrc/mw_mutate.h: the host twin
+// of mg_repair_leaves): base is nleaves x 8 limbs, cut here to each leaf's
+// width; the same refusals for mut, nmut and radius.
+int mwh_mutant_leaves(const mg_prog_desc* d, const uint32_t* base, const uint32_t* mut, size_t nmut, uint64_t seed,
+                      uint32_t radius, uint64_t m, uint32_t* out) {
+  if (!d || !base || !mut || !out) return mw_fail(MG_E_ARG, "null argument");
+  int rc = mg_validate_desc(d);
+  if (rc) return rc;
+  const u32 nl = (u32)d->nleaves;
+  if (const char* why = mutant_args_refused(d->leaves, nl, mut, nmut, radius)) return mw_fail(MG_E_ARG, why);
+  std::vector<u32> b(base, base + (size_t)nl * 8), prefix(nmut + 1);
+  for (u32 l = 0; l < nl; ++l) canon(b.data() + (size_t)l * 8, d->leaves[(size_t)l * MW_LEAF_WORDS + MW_LEAF_WIDTH]);
+  mutant_prefix(d->leaves, mut, (u32)nmut, prefix.data());
+  mutant_leaves(b.data(), d->leaves, nl, d->pool, mut, prefix.data(), (u32)nmut, seed, radius, m, out);
   return 0;
 }
 

@@ -10,6 +10,8 @@
 //                     objective (trace rows 0..7) instead of the lowest index:
 //                     a wave and block reduction over 256-bit keys, one record
 //                     per block, reduced by mw_min_reduce_kernel (mg_search_min).
+//   mw_repair_kernel  mw_eval_kernel over the mutants of an explicit base assignment
+//                     (mw_mutate.h), generated per lane (mg_search_repair).
 //   mw_keccak_kernel  one message per lane, Keccak-256.
 // Host side: context (device, stream, events, spill/min/counter buffers),
 // program upload with full validation, thread-local error strings.
@@ -41,6 +43,7 @@
 #include "mw_leaf.h"
 #include "mw_lex.h"
 #include "mw_min.h"
+#include "mw_mutate.h"
 
 extern "C" int mw_fail(int code, const char* msg);
 extern "C" int mg_validate_desc(const mg_prog_desc* d);
@@ -183,6 +186,29 @@ struct EvalEnv : SpillEnv {
       for (int k = 0; k < n; ++k) trace[((u64)row + k) * ncand + idx] = v[k];
   }
   __device__ bool none(bool) { return false; }  // eval: never exit early
+  DivCount dsteps;
+};
+
+// mg_search_repair's candidates: mutant `cand` of an explicit base assignment
+// (mw_mutate.h).  The mutant's picks are decoded once per candidate into eight
+// registers; a leaf is its base value (li is uniform: a uniform load) with the
+// picks on that leaf applied.  store and none are EvalEnv's.
+struct RepairEnv : SpillEnv {
+  const u32* __restrict__ leaves;
+  const u32* __restrict__ pool;
+  const u32* __restrict__ base;   // nleaves x 8 limbs, canonical
+  u32* __restrict__ trace;
+  u64 ncand;
+  u64 idx;   // candidate position within this launch
+  u64 seed;
+  u64 cand;  // mutant index
+  MutPicks picks;
+  __device__ void leaf(u32 li, u32 out[8]) { mutant_leaf(base, leaves, pool, seed, cand, picks, li, out); }
+  __device__ void store(u32 row, const u32* v, int n) {
+    if (trace)
+      for (int k = 0; k < n; ++k) trace[((u64)row + k) * ncand + idx] = v[k];
+  }
+  __device__ bool none(bool) { return false; }
   DivCount dsteps;
 };
 
@@ -669,6 +695,33 @@ __global__ __launch_bounds__(kBlock, 2) void mw_eval_kernel(ProgDev P, const u32
   }
 }
 
+// mg_search_repair's evaluation: mw_eval_kernel's chunk loop over mutants
+// [begin, begin + ncand) of the base assignment at `base` (mw_mutate.h; mut and
+// prefix are the call's mutable leaves and their width prefix sums, nmut and
+// nmut + 1 words).  A thread decodes its mutant once, the prefix searched in
+// global memory (at most 10 steps, only for the mutants below prefix[nmut]);
+// a thread past ncand decodes in bounds too and stores nothing.
+__global__ __launch_bounds__(kBlock, 2) void mw_repair_kernel(ProgDev P, const u32* __restrict__ base,
+                                                           const u32* __restrict__ mut,
+                                                           const u32* __restrict__ prefix, u32 nmut, u32 radius,
+                                                           u64 ncand, u64 seed, u64 begin,
+                                                           u32* __restrict__ verdict,
+                                                           u32* __restrict__ trace,
+                                                           u32* __restrict__ spillbuf, u32 nlds) {
+  const u64 nthreads = (u64)gridDim.x * kBlock;
+  const u64 gtid = (u64)blockIdx.x * kBlock + threadIdx.x;
+  const u64 nchunks = (ncand + kBlock - 1) / kBlock;
+  for (u64 ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+    const u64 idx = ch * kBlock + threadIdx.x;
+    const bool valid = idx < ncand;
+    RepairEnv env{{nlds, spillbuf, nthreads, gtid}, P.leaves, P.pool, base, valid ? trace : nullptr, ncand,
+                  valid ? idx : 0, seed, begin + idx};
+    mutant_decode(mut, prefix, nmut, seed, radius, env.cand, env.picks);
+    const bool ok = mw_run(P.code, P.consts, env, valid, 0u);
+    if (valid) verdict[idx] = ok ? 1u : 0u;
+  }
+}
+
 // The leaf values of one candidate: one thread per leaf, the candidate
 // generator of every search engine (mw_leaf.h leaf_value), for mg_witness_leaves.
 // The witness evaluations of mg_search_end read the candidate index the
@@ -845,6 +898,8 @@ struct Prog {
   bool asm_ok = false;          // every opcode and leaf kind has a handler in mw_search_asm_kernel
   u8 asm_layout = kWide;        // the asm kernel adev is predecoded for (kAsmKernel)
   bool trace_full = false;      // STOREs cover every trace row: an evaluation needs no zeroed trace block
+  std::vector<u32> h_leaves, h_pool;   // the leaf table and the pool on the host (mw_repair.inc: mutants are
+                                       // decoded and their tables built there)
   ProgDev adev{};               // dev with code = its predecoded copy (mw_asm_predecode) and leaves =
                                 // the asm leaf table (asm_leaf_table), in d_buf
   // specialised kernels (mg_prog_attach_kernel): one per part, launched in order
@@ -1435,6 +1490,8 @@ int mg_init(int device, mg_ctx** out) {
           hipSuccess ||
       hipFuncSetAttribute((const void*)mw_eval_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) !=
           hipSuccess ||
+      hipFuncSetAttribute((const void*)mw_repair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) !=
+          hipSuccess ||
       hipFuncSetAttribute((const void*)mw_search_min_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                           lds_max) != hipSuccess ||
       hipFuncSetAttribute((const void*)mw_search_min_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1502,6 +1559,8 @@ static int load_locked(const std::shared_ptr<Ctx>& cref, const mg_prog_desc* d, 
   p->desc = *d;
   p->ops_per_eval = d->ops_per_eval;
   p->trace_full = trace_rows_covered(d);
+  if (d->nleaves) p->h_leaves.assign(d->leaves, d->leaves + d->nleaves * MW_LEAF_WORDS);
+  if (d->npool_words) p->h_pool.assign(d->pool, d->pool + d->npool_words);
   mark.step("pool_get", total * 4);
   p->d_buf = (u32*)pool_get(c, total * sizeof(u32), &p->buf_cls);
   if (!p->d_buf) return fail(MG_E_NOMEM, "program upload allocation failed");
@@ -1583,7 +1642,7 @@ static int load_locked(const std::shared_ptr<Ctx>& cref, const mg_prog_desc* d, 
     p->adev.code = p->d_buf + nc + nk + nl + np;
     p->adev.leaves = p->adev.code + nc + 8 + MW_ASM_NK;
   }
-  // the desc's host pointers are not retained
+  // the desc's host pointers are not retained (h_leaves and h_pool are copies)
   p->desc.code = nullptr;
   p->desc.consts = nullptr;
   p->desc.leaves = nullptr;
@@ -2352,7 +2411,8 @@ static LexPlan lexmin_plan(const Ctx* c, const Prog* p, u64 count, u64 tile, u32
 // the asm interpreter, then `extra`'s n_extra records, which land at
 // c->d_asmargs + tile_records(L)), the call's one upload, init() for the memsets
 // of the call's result buffers, then per tile the evaluation of its verdicts
-// and trace rows into vt (reused: the stream orders the tiles) and
+// and trace rows into vt (reused: the stream orders the tiles; `eval`, if
+// given, launches it instead of the plan's engine: mw_repair.inc) and
 // fold(n, tile_begin, d_v, d_t), which launches the tile's fold.  The caller has
 // sized every other buffer before: between the first launch and the caller's
 // synchronisation nothing allocates, frees or waits.
@@ -2360,10 +2420,12 @@ static size_t tile_records(const LexPlan& L) { return L.engine.kind == kAsm ? (s
 
 typedef std::function<hipError_t()> TileInit;
 typedef std::function<void(u64 n, u64 tile_begin, const u32* d_v, const u32* d_t)> TileFold;
+// a call's own evaluation launch of one tile on gx blocks (mg_search_repair: the plan's engine is the compiled one)
+typedef std::function<hipError_t(u64 n, u64 tile_begin, u32* d_v, u32* d_t, u64 gx)> TileEval;
 
 static int tiles_enqueue(Ctx* c, const Prog* p, uint64_t seed, uint64_t begin, uint64_t count, const LexPlan& L,
                          Scratch& vt, const AsmArgs* extra, size_t n_extra, const TileInit& init,
-                         const TileFold& fold) {
+                         const TileFold& fold, const TileEval* eval = nullptr) {
   const bool on_asm = L.engine.kind == kAsm;
   const size_t ntile_args = tile_records(L);
   int rc = ensure_launch(c, 1, ntile_args + n_extra);
@@ -2384,7 +2446,9 @@ static int tiles_enqueue(Ctx* c, const Prog* p, uint64_t seed, uint64_t begin, u
   for (u64 t = 0; t < L.ntiles; ++t) {
     const u64 n = tile_n(t), tb = begin + t * L.tile;
     if (nrows && !p->trace_full) HIPCHK(hipMemsetAsync(d_t, 0, (size_t)nrows * n * 4, c->stream));
-    if (on_asm) {
+    if (eval) {
+      HIPCHK((*eval)(n, tb, d_v, d_t, tile_gx(n)));
+    } else if (on_asm) {
       rc = launch_eval_asm(c, p, false, c->d_asmargs + t, tile_gx(n), L.nlds);
       if (rc) return rc;
     } else {
@@ -2558,6 +2622,7 @@ int mg_search_blame(mg_ctx* h, mg_prog* hp, uint64_t seed, uint64_t begin, uint6
 }
 
 #include "mw_collect.inc"   // mg_search_collect: the tiles again, a count and a scatter kernel per tile
+#include "mw_repair.inc"    // mg_search_repair: the tiles over mutants of a base assignment, mg_search_blame's fold
 
 // One-shot evaluation of a program that is not kept (a witness program:
 // engine.WitnessEngine._materialize_traced): upload, evaluation and release

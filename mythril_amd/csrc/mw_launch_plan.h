@@ -389,4 +389,30 @@ inline CollectPlan plan_search_collect(const ProgFacts& facts, u64 count, u64 ti
   return C;
 }
 
+// mg_search_repair: plan_search_lexmin's tiles and fold grid with the engine
+// fixed to the compiled interpreter (the mutants of mw_mutate.h are generated
+// by mw_repair_kernel alone), each tile folded by mw_blame_fold_kernel as
+// mg_search_blame's: 2 launches per tile.  With nrows == 0 the tile's verdicts
+// are the one row.  The call's table (the base assignment's nleaves x 8 limbs,
+// the nmut mutable leaves, their nmut + 1 prefix sums) travels in the launch
+// block behind the launch records.
+struct RepairPlan {
+  LexPlan tiles;             // engine kCompiled always
+  u32 fold_rows = 1;         // rows the fold walks: nrows, or the verdicts as one
+  size_t total_bytes = 0;    // mw_blame.h's totals for fold_rows rows
+  size_t table_words = 0;    // base, mutable, prefix
+  size_t nlaunches = 0;      // 2 per tile
+};
+
+inline RepairPlan plan_search_repair(const ProgFacts& facts, u64 count, u64 tile, u32 nrows, u32 n_trace_rows,
+                                     u32 nleaves, u32 nmut, int ncu) {
+  RepairPlan R;
+  R.tiles = plan_search_lexmin(facts, count, tile, 0, n_trace_rows, ncu, false, 0);
+  R.fold_rows = nrows ? nrows : 1u;
+  R.total_bytes = (size_t)(2 * (u64)R.fold_rows + 2) * sizeof(u64);
+  R.table_words = (size_t)nleaves * 8 + 2 * (size_t)nmut + 1;
+  R.nlaunches = (size_t)(2 * R.tiles.ntiles);
+  return R;
+}
+
 }  // namespace mw

@@ -546,6 +546,8 @@ def _objectives_program(q: "Query", objectives: Sequence[Node]) -> Program:
 
 BLAME_MAX_ROWS = 1024     # include/mythril_witness.h mg_search_blame (csrc/mw_blame.h kBlameMaxRows)
 COLLECT_MAX = 65536       # include/mythril_witness.h mg_search_collect (csrc/mw_collect.h kCollectMaxCap)
+REPAIR_MAX_MUTABLE = 1024  # include/mythril_witness.h mg_search_repair (csrc/mw_mutate.h kRepairMaxMut)
+REPAIRED_INDEX = -1       # Witness.index of a witness WitnessEngine.repair built: no candidate index draws it
 CONGRUENCE = -1           # MissProfile: the congruence conjuncts' one bin, where conjunct numbers are listed
 
 
@@ -606,6 +608,24 @@ def _profile_program(q: "Query") -> Tuple[Program, List[int], Optional[int]]:
     if p.n_trace_rows != len(traced) or any(p.trace_map[t.id][1] != "N" for t in traced):
         raise EngineError("profile program: a conjunct is not one trace row")
     return p, [p.trace_map[t.id][0] for t in main], (p.trace_map[all_cong.id][0] if cong else None)
+
+
+def _leaf_limbs(values: Sequence[int]) -> np.ndarray:
+    """Leaf values as mg_witness_leaves lays them out: nleaves x 8 uint32 limbs."""
+    out = np.zeros((len(values), 8), dtype=np.uint32)
+    for i, v in enumerate(values):
+        for k in range(8):
+            out[i, k] = (int(v) >> (32 * k)) & 0xFFFFFFFF
+    return out
+
+
+def _leaf_rows(p: Program, limbs: np.ndarray) -> np.ndarray:
+    """mg_eval's SoA input rows (one candidate) from leaf limbs."""
+    rows = np.zeros((max(p.n_input_rows, 1), 1), dtype=np.uint32)
+    for li in range(len(p.leaf_nodes)):
+        r0, n = p.input_rows_for(li)
+        rows[r0:r0 + n, 0] = limbs[li, :n]
+    return rows
 
 
 def _combine_chunks(values: Dict[str, int], name: str, width: int) -> int:
@@ -858,6 +878,97 @@ class WitnessEngine:
             return found, total
         finally:
             dp.free()
+
+    def repair(self, q: Query, rounds: int = 8, count: Optional[int] = None, radius: int = 2,
+               profile: Optional[MissProfile] = None) -> Optional[Witness]:
+        """A witness of ``q`` from the neighbourhood of its nearest miss, or
+        None.  Starts from ``profile`` (or ``explain_miss(q)``): the base is
+        the nearest candidate's leaf values, the mutable leaves are the leaf
+        support of the conjuncts it fails (every leaf when the congruence bin
+        failed; the first 1024 of a larger support).  Each round runs the
+        profile program over the base's mutants (mg_search_repair,
+        csrc/mw_mutate.h): max(count, S) of them, S the summed widths of the
+        mutable leaves, so every one-bit change is always tried.  A mutant
+        that fails nothing is the witness; one that fails fewer rows becomes
+        the base, the failed set and its support are recomputed, and the next
+        round starts from it; a round without improvement, or ``rounds`` of
+        them, end with None.  A repaired witness is no candidate of the index
+        space: its ``index`` is REPAIRED_INDEX.  Like every witness it is
+        re-checked before use (model.py).  Raises Unsupported on a device
+        without ``search_repair`` (a multi-device engine)."""
+        if not hasattr(self.dev, "search_repair"):
+            raise Unsupported("this device has no search_repair")
+        prof = profile if profile is not None else self.explain_miss(q)
+        if prof.nearest is None:
+            return None
+        if prof.nearest_nfail == 0:
+            return prof.nearest
+        p, rows, crow = _profile_program(q)
+        nl = len(p.leaf_nodes)
+        if nl == 0 or p.n_trace_rows == 0:
+            return None
+        low = q.lowered
+        by_row: Dict[int, List[Node]] = {}
+        for j, r in enumerate(rows):
+            by_row.setdefault(r, []).append(low.conjuncts[j])
+        names = {n.name: i for i, n in enumerate(p.leaf_nodes)}
+        widths = [s.width for s in p.leaf_specs]
+
+        def failed_rows(dp, base) -> List[int]:
+            _, tr = self.dev.eval(dp, _leaf_rows(p, base), 1)
+            return [r for r in range(p.n_trace_rows) if not int(tr[r, 0])]
+
+        def support(failed: List[int]) -> List[int]:
+            if crow is not None and crow in failed:
+                return list(range(nl))[:REPAIR_MAX_MUTABLE]
+            terms = [t for r in failed for t in by_row.get(r, [])]
+            hit = sorted({names[v.name] for v in _free_vars(terms, q.ctx) if v.name in names})
+            return hit[:REPAIR_MAX_MUTABLE]
+
+        self.last_repair = {"rounds": 0, "nfail": prof.nearest_nfail}
+        dp = self.dev.load(p)
+        try:
+            base = _leaf_limbs(self.dev.witness_leaves(dp, self.seed, prof.nearest.index))
+            failed = failed_rows(dp, base)
+            self.last_repair["nfail"] = len(failed)
+            for rnd in range(rounds):
+                if not failed:
+                    break
+                mutable = support(failed)
+                if not mutable:
+                    return None
+                n = max(count or self.launch_count([q]), sum(widths[i] for i in mutable))
+                seed = (self.seed + rnd) & ((1 << 64) - 1)
+                idx, nfail, _, st = self.dev.search_repair(dp, base, mutable, seed, radius, 0, n, 0, p.n_trace_rows)
+                self.stats["evals"] += st["evals"]
+                self.stats["kernel_ms"] += st["kernel_ms"]
+                self.last_repair["rounds"] = rnd + 1
+                if nfail >= len(failed):
+                    return None
+                base = self.dev.repair_leaves(dp, base, mutable, seed, radius, idx)
+                failed = failed_rows(dp, base)
+                self.last_repair["nfail"] = len(failed)
+                if len(failed) != nfail:
+                    from .runtime import EngineError
+                    raise EngineError("repair: the mutant's leaves do not reproduce the search's failed rows")
+            if failed:
+                return None
+        finally:
+            dp.free()
+        values = {n.name: sum(int(base[i, k]) << (32 * k) for k in range(8)) for i, n in enumerate(p.leaf_nodes)}
+        if all(t.op == "const" for t in q.arg_terms):
+            w = self._from_leaves(q, REPAIRED_INDEX, [values[n.name] for n in q.program.leaf_nodes])
+        else:
+            from .runtime import pack_inputs
+            tp = q.trace_program
+            tdp = self.dev.load(tp)
+            try:
+                _, trace = self.dev.eval(tdp, pack_inputs(tp, [values]), 1)
+            finally:
+                tdp.free()
+            w = self._decode_trace(q, tp, REPAIRED_INDEX, trace)
+        self.stats["hits"] += 1
+        return w
 
     def _assemble(self, dps) -> None:
         """Attach assembled kernels to the eligible programs (parallel

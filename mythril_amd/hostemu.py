@@ -40,6 +40,9 @@ def lib():
         L.mwh_search_min.restype = ctypes.c_int
         L.mwh_search_min.argtypes = [ctypes.POINTER(MgProgDesc), ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                      ctypes.POINTER(MgMinResult)]
+        L.mwh_mutant_leaves.restype = ctypes.c_int
+        L.mwh_mutant_leaves.argtypes = [ctypes.POINTER(MgProgDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                        ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p]
         L.mg_last_error.restype = ctypes.c_char_p
         _lib = L
     return _lib
@@ -142,6 +145,84 @@ def search_collect(p: Program, seed: int, begin: int, n: int, cap: int, row: int
             rows.append(np.asarray(tr)[row:row + nrows][:, keep].T)
     out = np.concatenate(rows).astype(np.uint32) if rows else np.zeros((len(indices), nrows), dtype=np.uint32)
     return indices, out, total
+
+
+def leaf_limbs(p: Program, seed: int, index: int) -> np.ndarray:
+    """The leaf values (nleaves x 8 limbs, uint32) of generated candidate
+    ``index``: the host twin of mg_witness_leaves (mwh_leaf_values)."""
+    d, keep = make_desc(p)
+    out = np.zeros(max(1, len(p.leaf_nodes)) * 8, dtype=np.uint32)
+    f = lib().mwh_leaf_values
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.POINTER(MgProgDesc), ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
+    rc = f(ctypes.byref(d), seed & ((1 << 64) - 1), index, out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(lib().mg_last_error().decode())
+    return out[:len(p.leaf_nodes) * 8].reshape(-1, 8)
+
+
+def _mutant_args(p: Program, base, mutable):
+    nl = len(p.leaf_nodes)
+    b = np.ascontiguousarray(base, dtype=np.uint32).reshape(-1)
+    if b.size != 8 * nl:
+        raise RuntimeError("search_repair: base is nleaves x 8 limbs")
+    if any(not 0 <= int(x) < 1 << 32 for x in mutable):
+        raise RuntimeError("search_repair: a mutable leaf is not a leaf of the program")
+    return b, np.ascontiguousarray(list(mutable), dtype=np.uint32)
+
+
+def mutant_leaves(p: Program, base, mutable, seed: int, radius: int, m: int) -> np.ndarray:
+    """The leaf values (nleaves x 8 limbs, uint32) of mutant m of ``base``
+    (the same layout) with the leaves ``mutable`` free to change: csrc/mw_mutate.h's
+    rule through mwh_mutant_leaves, the host twin of mg_repair_leaves."""
+    b, mut = _mutant_args(p, base, mutable)
+    d, keep = make_desc(p)
+    out = np.zeros(max(1, b.size), dtype=np.uint32)
+    rc = lib().mwh_mutant_leaves(ctypes.byref(d), b.ctypes.data if b.size else None, mut.ctypes.data if mut.size else None,
+                                 mut.size, seed & ((1 << 64) - 1), radius, m, out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(lib().mg_last_error().decode())
+    return out[:b.size].reshape(-1, 8)
+
+
+def leaves_soa(p: Program, limbs: Sequence[np.ndarray]) -> np.ndarray:
+    """mg_eval's SoA input rows from per-candidate leaf limbs (nleaves x 8 each)."""
+    rows = np.zeros((max(p.n_input_rows, 1), len(limbs)), dtype=np.uint32)
+    for li in range(len(p.leaf_nodes)):
+        r0, nl = p.input_rows_for(li)
+        for j, v in enumerate(limbs):
+            rows[r0:r0 + nl, j] = v[li, :nl]
+    return rows
+
+
+def search_repair(p: Program, base, mutable, seed: int, radius: int, begin: int, n: int, row: int = 0,
+                  nrows: int = 0, chunk: int = 1 << 10):
+    """(index, nfail, satisfied) over mutants [begin, begin+n) of ``base``:
+    the mutant of lowest (failed rows among p's trace rows [row, row+nrows),
+    index) and how many fail none; with nrows == 0 p's verdict is the one row.
+    The CPU twin of mg_search_repair: the mutants built by mwh_mutant_leaves,
+    sent through mwh_eval's SoA inputs; the same key and the same refusals."""
+    if n <= 0 or begin < 0 or begin + n > 1 << 48:
+        raise RuntimeError("search_repair: a non-empty range of mutant indices below 2^48")
+    if not 0 <= nrows <= 1024 or (nrows and (row < 0 or row + nrows > p.n_trace_rows)):
+        raise RuntimeError("search_repair: at most 1024 of the program's trace rows")
+    d, keep = make_desc(p)
+    satisfied, near = 0, None
+    for at in range(0, n, chunk):
+        k = min(chunk, n - at)
+        soa = leaves_soa(p, [mutant_leaves(p, base, mutable, seed, radius, begin + at + j) for j in range(k)])
+        v = np.zeros(k, dtype=np.uint32)
+        t = np.zeros(max(p.n_trace_rows, 1) * k, dtype=np.uint32)
+        rc = lib().mwh_eval(ctypes.byref(d), soa.ctypes.data, 0, 0, k, 0, v.ctypes.data, t.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(lib().mg_last_error().decode())
+        rows = t.reshape(max(p.n_trace_rows, 1), k)[row:row + nrows] if nrows else v.reshape(1, k)
+        nfail = (rows == 0).sum(axis=0)
+        satisfied += int((nfail == 0).sum())
+        j = int(np.argmin(nfail))          # the first of the lowest
+        if near is None or int(nfail[j]) < near[0]:
+            near = (int(nfail[j]), begin + at + j)
+    return near[1], near[0], satisfied
 
 
 def eval_generated(p: Program, seed: int, begin: int, n: int):

@@ -163,6 +163,24 @@ WITNESS_RETRIES = max(0, int(os.environ.get("MYTHRIL_AMD_WITNESS_RETRIES", "0"))
 WITNESS_RETRIES_MAX = 1 << 16   # mg_search_collect's room
 
 
+# MYTHRIL_AMD_REPAIR=N: after a single-query miss, N rounds of neighbourhood
+# search around the nearest candidate (WitnessEngine.repair, mg_search_repair)
+# before z3; a repaired witness goes through the usual z3 re-check.  0 (the
+# default): off.
+REPAIR = max(0, int(os.environ.get("MYTHRIL_AMD_REPAIR", "0")))
+
+
+def _repair_miss(eng, q):
+    try:
+        w = eng.repair(q, rounds=REPAIR)
+    except Exception as e:   # noqa: BLE001 - as around the search: the reference answers
+        log.debug("witness engine: repair failed (%s)", e)
+        return None
+    if w is not None:
+        STATS["repaired"] = STATS.get("repaired", 0) + 1
+    return w
+
+
 def _profile_miss(eng, q) -> None:
     try:
         m = eng.explain_miss(q, count=min(eng.budget, MISS_PROFILE_MAX))
@@ -226,6 +244,8 @@ def _gpu_model(constraints, timeout):
             STATS["device_errors"] = STATS.get("device_errors", 0) + 1
             log.warning("witness engine: device error (%s); z3 answers", e)
             return None
+        if witness is None and REPAIR:
+            witness = _repair_miss(eng, q)
         if witness is None:
             _record_miss(raws, key)
             if MISS_PROFILE:

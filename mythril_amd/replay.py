@@ -9,12 +9,16 @@ device, many programs per launch.  It gives offline replays and benchmarks of
 real analyses without z3 or solc.
 
     python -m mythril_amd.replay DIR [--budget 2^22] [--batch 64] [--explain-misses] [--witness-density]
+                                     [--repair-misses]
 
 ``--explain-misses`` profiles every missed query (WitnessEngine.explain_miss)
 and prints one more line for it: which conjuncts reject its candidates.
 ``--witness-density`` counts every searched query's witnesses
 (WitnessEngine.search_all) and prints one more line for it: how many of its
 candidates are witnesses, and the first of them.
+``--repair-misses`` runs WitnessEngine.repair on every missed query and prints
+one more line for it: repaired or not, the rounds used and the final number of
+failed conjunct rows.
 """
 from __future__ import annotations
 
@@ -41,6 +45,7 @@ class Result:
     functions: dict = field(default_factory=dict)   # UF -> {args: value}
     profile: Optional[object] = None                # a miss under explain: engine.MissProfile (or the error's text)
     density: Optional[object] = None                # under density: (total, count, first index or None) (or the error's text)
+    repair: Optional[object] = None                 # a miss under repair: {"witness", "rounds", "nfail"} (or the error's text)
 
 
 def load(path: str):
@@ -82,7 +87,22 @@ def density_line(r: Result) -> str:
     return f"density {name}: {total} / {count} witnesses, first {'none' if first is None else first}"
 
 
-def replay(paths: List[str], engine, batch: int = 64, explain: bool = False, density: bool = False) -> List[Result]:
+REPAIR_ROUNDS = 8   # --repair-misses
+
+
+def repair_line(r: Result) -> str:
+    """One line for a miss WitnessEngine.repair was run on: repaired or not,
+    the rounds it used and the conjunct rows the last base still fails."""
+    name = os.path.basename(r.path)
+    d = r.repair
+    if d is None or isinstance(d, str):
+        return f"miss {name}: no repair ({d})"
+    return (f"miss {name}: {'repaired' if d['witness'] is not None else 'not repaired'}, rounds {d['rounds']}, "
+            f"nfail {d['nfail']}")
+
+
+def replay(paths: List[str], engine, batch: int = 64, explain: bool = False, density: bool = False,
+           repair: int = 0, repair_count: Optional[int] = None) -> List[Result]:
     out: List[Result] = []
     pending = []
     for p in paths:
@@ -106,6 +126,13 @@ def replay(paths: List[str], engine, batch: int = 64, explain: bool = False, den
                         out[-1].profile = engine.explain_miss(q, count=min(engine.budget, EXPLAIN_MAX))
                     except Exception as e:   # noqa: BLE001 - a diagnostic: the miss stands
                         out[-1].profile = f"{type(e).__name__}: {e}"
+                if repair:
+                    try:
+                        prof = out[-1].profile if explain and not isinstance(out[-1].profile, str) else None
+                        w2 = engine.repair(q, rounds=repair, count=repair_count, profile=prof)
+                        out[-1].repair = {"witness": w2, **getattr(engine, "last_repair", {"rounds": 0, "nfail": 0})}
+                    except Exception as e:   # noqa: BLE001 - a diagnostic: the miss stands
+                        out[-1].repair = f"{type(e).__name__}: {e}"
             else:
                 out.append(Result(p, "witness", w.index, dict(w.values), arrays=w.arrays, functions=w.functions))
             if density:
@@ -129,6 +156,8 @@ def main(argv=None):
                     help="profile every missed query: one line with its blocking conjuncts")
     ap.add_argument("--witness-density", action="store_true",
                     help="count every searched query's witnesses: one line with total / count and the first index")
+    ap.add_argument("--repair-misses", action="store_true",
+                    help="run WitnessEngine.repair on every missed query: one line with repaired or not, rounds, nfail")
     a = ap.parse_args(argv)
     files = []
     for p in a.paths:
@@ -137,13 +166,16 @@ def main(argv=None):
     from .engine import WitnessEngine
     eng = WitnessEngine(device=a.device, budget=a.budget)
     t0 = time.perf_counter()
-    res = replay(files, eng, a.batch, explain=a.explain_misses, density=a.witness_density)
+    res = replay(files, eng, a.batch, explain=a.explain_misses, density=a.witness_density,
+                 repair=REPAIR_ROUNDS if a.repair_misses else 0)
     dt = time.perf_counter() - t0
     for r in res:
         print(json.dumps({"file": os.path.basename(r.path), "status": r.status, "index": r.index,
                           "reason": r.reason}))
         if a.explain_misses and r.status == "miss":
             print(explain_line(r))
+        if a.repair_misses and r.status == "miss":
+            print(repair_line(r))
         if a.witness_density and r.status in ("witness", "miss"):
             print(density_line(r))
     summary = {k: sum(1 for r in res if r.status == k) for k in ("witness", "miss", "z3", "unsupported")}

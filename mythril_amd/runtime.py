@@ -92,6 +92,12 @@ class MgCollectResult(ctypes.Structure):
     _fields_ = [("total", ctypes.c_uint64), ("stored", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class MgRepairResult(ctypes.Structure):
+    """include/mythril_witness.h mg_repair_result"""
+    _fields_ = [("index", ctypes.c_uint64), ("nfail", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("satisfied", ctypes.c_uint64)]
+
+
 _P = ctypes.c_void_p
 _lib = None
 _lib_lock = threading.Lock()
@@ -128,6 +134,11 @@ SIGNATURES = {
     "mg_search_collect": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
                                          ctypes.c_uint32, ctypes.c_uint64, _P, _P, ctypes.c_size_t,
                                          ctypes.POINTER(MgCollectResult), ctypes.POINTER(MgStats)]),
+    "mg_search_repair": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32,
+                                        ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                        ctypes.c_uint64, ctypes.POINTER(MgRepairResult), ctypes.POINTER(MgStats)]),
+    "mg_repair_leaves": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32,
+                                        ctypes.c_uint64, _P]),
     "mg_eval": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t, _P, _P]),
     "mg_eval_generated": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t, _P, _P]),
     "mg_witness_leaves": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, _P]),
@@ -384,6 +395,47 @@ class Device:
                "mg_search_collect")
         k = int(out.stored)
         return [int(v) for v in idx[:k]], rows[:k].copy(), int(out.total), st.as_dict()
+
+    @staticmethod
+    def _repair_args(dp: DeviceProgram, base, mutable):
+        b = np.ascontiguousarray(base, dtype=np.uint32).reshape(-1)
+        if b.size != 8 * len(dp.prog.leaf_nodes):
+            raise EngineError("base is nleaves x 8 limbs")
+        if any(not 0 <= int(x) < 1 << 32 for x in mutable):
+            raise EngineError("a mutable leaf is not a leaf of the program")
+        return b, np.ascontiguousarray(list(mutable), dtype=np.uint32)
+
+    def search_repair(self, dp: DeviceProgram, base, mutable: Sequence[int], seed: int, radius: int, begin: int,
+                      count: int, row: int = 0, nrows: int = 0, tile: int = 0) -> Tuple[int, int, int, dict]:
+        """mg_search_repair: (index, nfail, satisfied, stats) over mutants
+        [begin, begin+count) of ``base`` (nleaves x 8 uint32 limbs,
+        witness-leaves layout) with the leaves ``mutable`` (ascending
+        indices) free to change, at most ``radius`` of them per mutant
+        (csrc/mw_mutate.h).  index is the mutant that fails the fewest of dp's
+        trace rows [row, row+nrows) (nfail of them; nrows == 0: dp's verdict is
+        the one row), ties to the lowest index; satisfied counts the mutants
+        that fail none.  tile: as search_lexmin's."""
+        if self._reap_queue:
+            self._reap()
+        b, mut = self._repair_args(dp, base, mutable)
+        out = MgRepairResult()
+        st = MgStats()
+        _check(self.lib, self.lib.mg_search_repair(self.handle, dp.handle, _ptr(b), _ptr(mut), mut.size,
+                                                   seed & ((1 << 64) - 1), radius, begin, count, row, nrows, tile,
+                                                   ctypes.byref(out), ctypes.byref(st)), "mg_search_repair")
+        return int(out.index), int(out.nfail), int(out.satisfied), st.as_dict()
+
+    def repair_leaves(self, dp: DeviceProgram, base, mutable: Sequence[int], seed: int, radius: int,
+                      index: int) -> np.ndarray:
+        """mg_repair_leaves: the leaf values (nleaves x 8 uint32 limbs) of
+        mutant ``index`` of the same base, mutable leaves, seed and radius:
+        what search_repair evaluated there.  Computed on the host."""
+        b, mut = self._repair_args(dp, base, mutable)
+        out = np.zeros(max(1, b.size), dtype=np.uint32)
+        _check(self.lib, self.lib.mg_repair_leaves(self.handle, dp.handle, _ptr(b), _ptr(mut), mut.size,
+                                                   seed & ((1 << 64) - 1), radius, index, out.ctypes.data),
+               "mg_repair_leaves")
+        return out[:b.size].reshape(-1, 8)
 
     def search_begin(self, progs: Sequence[DeviceProgram], seed: int, begin: int, count: int,
                      flags: int = 0) -> None:
