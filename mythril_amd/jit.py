@@ -57,6 +57,11 @@ CHECK_SYNC_EVERY = int(os.environ.get("MW_JIT_CHECK_SYNC_EVERY", "1"))   # ... a
 # v_mad_u64_u32 carry-outs counted per column) instead of mul8's rows; C5
 # 17.51 -> 17.40 ms per 2^22 launch (profiles/r6k/ab_c5_mulcols.json)
 MUL_COLS = os.environ.get("MW_JIT_MUL_COLS", "1") == "1"
+# A product of a register and a literal with 8 nonzero limbs by columns too
+# (the literal's limbs moved into registers: 65 VALU instructions against the
+# rows' 114); a literal with a zero limb keeps mul8's rows, which LLVM folds.
+# "0" emits the source without them, line for line
+MULK_COLS = os.environ.get("MW_JIT_MULK_COLS", "1") == "1"
 # An LDS leaf's reload is placed up to this many body lines before its use
 # (not before the leaf's own store, and not above a division: LDS_AHEAD_STOP),
 # so its latency overlaps the instructions in between; 0 reloads right before
@@ -286,14 +291,23 @@ def range_sites(p: Program, insns: Optional[Sequence[MInsn]] = None) -> Dict[str
     return out
 
 
+def _full_literal_product(srcs) -> bool:
+    """A register times a literal whose 8 limbs are all nonzero."""
+    if len(srcs) != 2 or sum(isinstance(s, Const) for s in srcs) != 1:
+        return False
+    v = next(s for s in srcs if isinstance(s, Const)).value & M256
+    return all((v >> (32 * k)) & M32 for k in range(8))
+
+
 class _Gen:
     """Emit the body of one program as straight-line HIP."""
 
     def __init__(self, p: Program, name: str, fence_first: bool = False, lds_leaves: int = 0,
                  insns: Optional[List[MInsn]] = None, interleave: int = 1, mul_cols: Optional[bool] = None,
-                 ranges: Optional[bool] = None):
+                 ranges: Optional[bool] = None, mulk_cols: Optional[bool] = None):
         self.fence_first = fence_first  # diagnostics (tools/opbench.py): no folding across nodes
         self.mul_cols = MUL_COLS if mul_cols is None else mul_cols
+        self.mulk_cols = self.mul_cols and (MULK_COLS if mulk_cols is None else mulk_cols)
         self.p = p
         self.insns = interleave_conjuncts(p.machine_ir() if insns is None else insns, interleave)
         # static bit bounds of the wide values (None: the range-specialised helpers are off)
@@ -421,6 +435,8 @@ class _Gen:
                 out(f"u32 {dn}[8]; jit::w_mul_nb<{na}, {nb}>({A[0]}, {A[1]}, {w}u, {dn});")
             else:
                 out(f"u32 {dn}[8]; jit::w_mulv({A[0]}, {A[1]}, {w}u, {dn});")
+        elif op == "W_MUL" and self.mulk_cols and _full_literal_product(S):
+            out(f"u32 {dn}[8]; jit::w_mulv({A[0]}, {A[1]}, {w}u, {dn});")
         elif op in _WBIN:
             out(f"u32 {dn}[8]; jit::{_WBIN[op]}({A[0]}, {A[1]}, {w}u, {dn});")
         elif op.startswith("W_") and op[2:] in _DIV:
@@ -605,7 +621,8 @@ def split_ssa(p: Program, part_weight: int = PART_WEIGHT) -> List[List[MInsn]]:
 def generate(progs: Sequence[Program], names: Sequence[str], variants: str = "xe",
              fence_first: bool = False, lds_leaves: int = 0,
              parts: Optional[Sequence[Tuple[List[MInsn], int, int]]] = None, interleave: int = 1,
-             mul_cols: Optional[bool] = None, ranges: Optional[bool] = None) -> str:
+             mul_cols: Optional[bool] = None, ranges: Optional[bool] = None,
+             mulk_cols: Optional[bool] = None) -> str:
     """HIP source for a module holding one specialised kernel set per program
     (with `parts`: per program, its (instructions, part index, part count))."""
     out = ["// generated by mythril_amd/jit.py: specialised witness-search kernels"]
@@ -631,7 +648,8 @@ def generate(progs: Sequence[Program], names: Sequence[str], variants: str = "xe
         part = parts[k] if parts else None
         out.append(f"// program {name}: {p.n_insn} bytecode insns, {p.ops_per_eval} u32 ops/eval"
                    + (f", part {part[1]} of {part[2]}" if part else ""))
-        out.append(_Gen(p, name, fence_first, lds_leaves, part[0] if part else None, interleave, mul_cols, ranges).body())
+        out.append(_Gen(p, name, fence_first, lds_leaves, part[0] if part else None, interleave, mul_cols, ranges,
+                        mulk_cols).body())
         out.append(f"MW_JIT_SIG({name}, {signature(p):#x}ull)")
         if part:
             out.append(f"MW_JIT_PART({name}, {part[1]}u, {part[2]}u)")
@@ -717,17 +735,21 @@ def is_cached(progs: Sequence[Program], variants: str = "xe", waves: int = 2, ld
 
 def compile_device(progs: Sequence[Program], variants: str = "xe", fence_first: bool = False,
                    waves: int = 2, lds_leaves: int = 0, interleave: int = 1,
-                   mul_cols: Optional[bool] = None, ranges: Optional[bool] = None) -> Tuple[bytes, List[str], float]:
+                   mul_cols: Optional[bool] = None, ranges: Optional[bool] = None,
+                   mulk_cols: Optional[bool] = None,
+                   extra_flags: Sequence[str] = ()) -> Tuple[bytes, List[str], float]:
     """gfx950 code object for `progs`; returns (image, kernel names, compile seconds; 0 if cached).
-    ranges: the range pass on or off for this module (None: the RANGES switch).
+    ranges: the range pass on or off for this module (None: the RANGES switch);
+    mulk_cols likewise for MULK_COLS.  extra_flags: further compiler flags for
+    this module alone (the -DMW_JIT_* switches of mw_jit.h), part of the cache key.
 
     waves: waves per SIMD the kernels are built for (launch bounds): 2 gives
     each lane 256 registers, 1 gives 512 (AGPRs become spill space instead of
     scratch memory) at half the latency hiding."""
     names = [kernel_name(p) for p in progs]
     src = generate(progs, names, variants, fence_first, lds_leaves, interleave=interleave, mul_cols=mul_cols,
-                   ranges=ranges)
-    path, dt = _compile(src, _device_flags(waves), ".hsaco", ".hip")
+                   ranges=ranges, mulk_cols=mulk_cols)
+    path, dt = _compile(src, _device_flags(waves) + list(extra_flags), ".hsaco", ".hip")
     return path.read_bytes(), names, dt
 
 

@@ -84,7 +84,23 @@ VARIANTS = {"base": {"EXTRA_FLAGS": []},
             "ranges": {"EXTRA_FLAGS": [], "RANGES": True}, "noranges": {"EXTRA_FLAGS": [], "RANGES": False},
             # the same kernel as "noranges" under a second name: the spread of repeated runs
             "noranges2": {"EXTRA_FLAGS": [], "RANGES": False},
-            "ranges_div": {"EXTRA_FLAGS": [], "RANGES": True, "RANGES_MUL": False}}
+            "ranges_div": {"EXTRA_FLAGS": [], "RANGES": True, "RANGES_MUL": False},
+            # half-rate issue (mw_jit.h, DESIGN.md "Half-rate issue"): each switch on (the
+            # default kernel under the switch's name) and off.  Ordered compares as a borrow
+            # chain / as LLVM's v_cmp cascade; the same for compares with a literal operand alone
+            "cmp_on": {"EXTRA_FLAGS": []}, "cmp_off": {"EXTRA_FLAGS": ["-DMW_JIT_CMP_CASCADE"]},
+            "cmpk_on": {"EXTRA_FLAGS": []}, "cmpk_off": {"EXTRA_FLAGS": ["-DMW_JIT_CMPK_CASCADE"]},
+            # equality on one v_cmp after a fenced xor/or tree / as 8 v_cmp_eq (the default)
+            "eq_on": {"EXTRA_FLAGS": ["-DMW_JIT_EQ_ONE"]}, "eq_off": {"EXTRA_FLAGS": []},
+            # column 7 of mul8_cols as a v_mad_u64_u32 chain / as 8 v_mul_lo_u32 and adds (the default)
+            "col7_on": {"EXTRA_FLAGS": ["-DMW_JIT_MUL_COL7_MAD"]}, "col7_off": {"EXTRA_FLAGS": []},
+            # products by a full-width literal by columns / by rows (jit.MULK_COLS)
+            "mulk_on": {"EXTRA_FLAGS": [], "MULK_COLS": True}, "mulk_off": {"EXTRA_FLAGS": [], "MULK_COLS": False},
+            # everything off: the kernel before this work, from today's source
+            "hr_off": {"EXTRA_FLAGS": ["-DMW_JIT_CMP_CASCADE"],
+                       "MULK_COLS": False},
+            # the default kernel under a second name: the spread of repeated runs
+            "base2": {"EXTRA_FLAGS": []}}
 
 
 MUL_COLS_DEFAULT = jit.MUL_COLS
@@ -94,6 +110,7 @@ LDS_AHEAD_STOP_DEFAULT = jit.LDS_AHEAD_STOP
 SPLIT_EVERY_DEFAULT = jit.SPLIT_EVERY
 LDS_REUSE_DEFAULT = jit.LDS_REUSE
 RANGES_DEFAULT = jit.RANGES
+MULK_COLS_DEFAULT = jit.MULK_COLS
 
 
 def main():
@@ -108,7 +125,7 @@ def main():
     p = compile_program(syn.conjuncts)
     images = {}
     for v in a.variants.split(","):
-        opts = {"RANGES": RANGES_DEFAULT, "RANGES_MUL": True, "CHECK_SYNC": False, "CHECK_SYNC_EVERY": 1, "LDS_REUSE": LDS_REUSE_DEFAULT, "MUL_COLS": MUL_COLS_DEFAULT, "LDS_AHEAD": LDS_AHEAD_DEFAULT, "LDS_AHEAD_W": LDS_AHEAD_W_DEFAULT,
+        opts = {"MULK_COLS": MULK_COLS_DEFAULT, "RANGES": RANGES_DEFAULT, "RANGES_MUL": True, "CHECK_SYNC": False, "CHECK_SYNC_EVERY": 1, "LDS_REUSE": LDS_REUSE_DEFAULT, "MUL_COLS": MUL_COLS_DEFAULT, "LDS_AHEAD": LDS_AHEAD_DEFAULT, "LDS_AHEAD_W": LDS_AHEAD_W_DEFAULT,
                 "LDS_AHEAD_STOP": LDS_AHEAD_STOP_DEFAULT, "SPLIT_EVERY": SPLIT_EVERY_DEFAULT, **VARIANTS[v]}
         il = opts.pop("interleave", 1)
         waves, lds = opts.pop("waves", 2), opts.pop("lds", 10)

@@ -10,6 +10,13 @@ The list scheduler below issues each product as soon as its SGPR pair is
 free and each v_addc once two VALU instructions separate it from its v_mad
 (an s_nop only where the column runs out: column 1).
 
+The accumulator pair is an early-clobber in/out operand ("+&v"): every
+statement writes it before it has read all its inputs, and without the `&` LLVM
+may give an input that holds the same value as one of its halves (a literal zero
+limb against the zero high half a column starts from) that half's register.
+
+Column 7 (column7) keeps only its low word: the same chain without carries.
+
     python tools/gen_mul_cols.py          # prints the column statements
 """
 S = ["%[s0]", "%[s1]", "%[s2]"]
@@ -62,7 +69,7 @@ def statements() -> str:
         carry = k <= 5
         lines = column(k, carry)
         ins = ", ".join([f'[a{i}] "v"(a[{i}])' for i in range(k + 1)] + [f'[b{j}] "v"(b[{j}])' for j in range(k + 1)])
-        outs = '[p] "+v"(p)' + (', [c] "=&v"(c)' if carry else '') + \
+        outs = '[p] "+&v"(p)' + (', [c] "=&v"(c)' if carry else '') + \
             ', [s0] "=&s"(s0), [s1] "=&s"(s1), [s2] "=&s"(s2)'
         out.append(f"  // column {k}")
         out.append("  asm(" + "\n      ".join(f'"{x}\\n"' for x in lines))
@@ -74,5 +81,21 @@ def statements() -> str:
     return "\n".join(out)
 
 
+def column7() -> str:
+    """Column 7, which follows `r[6] = (u32)p;`: only its low word is part of
+    the product, so the chain starts from the carry word alone (p >>= 32) and
+    nobody reads its high half or its carry-outs: no wait states to keep."""
+    lines = column(7, False)
+    ins = ", ".join([f'[a{i}] "v"(a[{i}])' for i in range(8)] + [f'[b{j}] "v"(b[{j}])' for j in range(8)])
+    out = ["  p >>= 32;", "  // column 7",
+           "  asm(" + "\n      ".join(f'"{x}\\n"' for x in lines),
+           '      : [p] "+&v"(p), [s0] "=&s"(s0), [s1] "=&s"(s1), [s2] "=&s"(s2)',
+           f"      : {ins});",
+           "  r[7] = (u32)p;"]
+    return "\n".join(out)
+
+
 if __name__ == "__main__":
     print(statements())
+    print("  r[6] = (u32)p;")
+    print(column7())

@@ -48,6 +48,19 @@ def main():
         from tests.test_gpu_jit_ranges import range_test_programs
         print("tests/test_gpu_jit_ranges.py module:", jit.compile_device(range_test_programs())[2], "s", flush=True)
 
+    def halfrate():
+        from tests import halfrate as h
+        cmp_progs = [p for *_, p in h.compare_programs()]
+        for flags in ([], h.CMP_OFF_FLAGS, h.EQ_ONE_FLAGS):
+            print("tests/test_gpu_jit_halfrate.py compares %s:" % " ".join(flags),
+                  jit.compile_device(cmp_progs, variants="x", extra_flags=flags)[2], "s", flush=True)
+        for cols in (None, False):
+            print("tests/test_gpu_jit_halfrate.py constant products mulk_cols=%s:" % cols,
+                  jit.compile_device([h.mulk_program()[0]], variants="x", mulk_cols=cols)[2], "s", flush=True)
+        for flags in ([], h.COL7_ON_FLAGS):
+            print("tests/test_gpu_jit_halfrate.py column 7 %s:" % " ".join(flags),
+                  jit.compile_device([h.col7_program()[0]], variants="x", extra_flags=flags)[2], "s", flush=True)
+
     def opmatrix(ranges):
         from tests.opmatrix import jit_programs
         print("tests/test_gpu_opmatrix.py module ranges=%s:" % ranges,
@@ -59,7 +72,7 @@ def main():
               jit.compile_device(jit_programs(), variants="x", lds_leaves=lds_leaves)[2], "s", flush=True)
 
     from config_bench import warm_jobs as config_jobs   # tools/config_bench.py (C2-C4 solver-log queries)
-    jobs += config_jobs() + [gpu_jit_modules, constant_divisors, mul_cols]
+    jobs += config_jobs() + [gpu_jit_modules, constant_divisors, mul_cols, halfrate]
     jobs += [lambda: opmatrix(True), lambda: opmatrix(False)]
     from tests.leafmatrix import JIT_LDS_LEAVES
     jobs += [lambda: leafmatrix(0), lambda: leafmatrix(JIT_LDS_LEAVES)]
